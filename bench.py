@@ -14,6 +14,12 @@ the timed region starts.  The roofline object prices the dominant kernel with it
 duration.  Test infrastructure under oracle/ (liboracle.so through tests/oracle_lib.py) is used
 only as a checker outside the timed region: cpu_baseline (N = 1) and the bit-exact correctness
 check of the N > 1 results.
+
+A plain run sets up, warms up, times --steps steps and prints the line (N > 1: after tuning the launch
+shape, which the headline is measured at).  --full adds everything measured or checked beside the
+headline: the CPU and host-proxy baselines, same-run ceilings, staging, size sweeps, the default
+selector, the oracle checks, phase times, the xGMI probe and the graph-captured figures.
+--dump-outputs DIR writes the last timed step's result (float32 .npy, a seeded sample when large).
 """
 import argparse
 import ctypes
@@ -42,15 +48,42 @@ def parse():
     p.add_argument("--bytes", type=int, default=48 << 20)
     p.add_argument("--algo", default=None,
                    help="force an AllReduce algorithm (N>1): packet|allpair|fullmesh|rsag|rsag_zc|rsag_pipeline")
-    p.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline sample budget")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-extras", action="store_true", help="N>1: skip the LL latency sweep and the fp32 1 GiB run")
-    p.add_argument("--no-check", action="store_true", help="N>1: skip the per-candidate bit-exact checks")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: CPU and host-proxy baselines, same-run ceilings, staging, size sweeps, "
+                        "the correctness checks against the oracle, phase times and the xGMI probe (N>1).  Without it "
+                        "a run sets up, warms up, times --steps steps and prints the result line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed to DIR/<name>.npy (float32; "
+                        "a fixed seeded sample of an output above the size budget, 48 MiB over all ranks)")
+    p.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU baseline sample budget")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU and host-proxy baselines")
+    p.add_argument("--no-extras", action="store_true",
+                   help="--full: skip the ceilings, staging and sweeps (N>1: the LL sweep and the fp32 1 GiB run)")
+    p.add_argument("--no-check", action="store_true", help="--full, N>1: skip the per-candidate bit-exact checks")
     p.add_argument("--same-input", action="store_true", help="N>1 diagnostic: every step on the seq-1 input")
     p.add_argument("--dry-run", action="store_true",
                    help="launcher self-test: every rank checks its environment, rank 0 prints the rank layout")
     p.add_argument("--rank-timeout", type=float, default=1500.0, help="launcher: seconds before hung ranks are killed")
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:  # a plain run measures the headline alone
+        args.no_cpu_baseline = args.no_extras = args.no_check = True
+    return args
+
+
+DUMP_BUDGET = 48 << 20  # bytes of float32 data that --dump-outputs may write, over all ranks (limit: 64 MB of files)
+
+
+def dump_output(directory, name, t, budget):
+    """--dump-outputs: write tensor `t` as float32 to directory/name.npy.  An output above `budget`
+    bytes is cut to a sample of budget / 4 elements at sorted positions drawn without replacement
+    by a generator seeded with 0, so two runs with the same arguments write the same elements."""
+    os.makedirs(directory, exist_ok=True)
+    flat = t.detach().reshape(-1)
+    keep = budget // 4
+    if flat.numel() > keep:
+        idx = np.sort(np.random.default_rng(0).choice(flat.numel(), keep, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    np.save(os.path.join(directory, name + ".npy"), flat.float().cpu().numpy())
 
 
 def cpu_threads():
@@ -292,9 +325,12 @@ def bench_single(args):
     t = (time.perf_counter() - t0) / args.steps
     kern_ms = ev0.elapsed_time(ev1) / args.steps
     assert int(err[0].item()) == 0, "device error word set"
-    # correctness spot check of the last step
-    ref = (x.float() + y.float()).clamp(-65504, 65504).half()
-    assert torch.equal(out, ref), "self-reduce mismatch"
+    if args.dump_outputs:  # the last timed step's result, before anything below launches again
+        dump_output(args.dump_outputs, "out", out, DUMP_BUDGET)
+    if args.full:
+        # correctness spot check of the last step
+        ref = (x.float() + y.float()).clamp(-65504, 65504).half()
+        assert torch.equal(out, ref), "self-reduce mismatch"
     achieved = 7 * S / (kern_ms * 1e-3) / 1e9
     res = {
         "metric": "device-resident AllReduce algbw GB/s fp16 at 1/2/4/8 MI355X; % xGMI roofline",
@@ -748,21 +784,25 @@ def bench_multi(args):
     # ---- the built-in selector's choice, as a drop-in caller of ncclAllReduce gets it before any
     # tuning (algo None -> ncclAllReduce -> mscclppAmdSelectAlgo + its launch shape), timed like the
     # headline: the `default_selector` figure beside it
-    progress("default selector")
-    default_sel = {"algo": SELECT_NAMES[m.lib().mscclppAmdSelectAlgo(n, S, 0)],
-                   "source": m.tuned_config_source("allreduce", n, S)}
-    try:
-        for j in range(3):
-            comm.all_reduce(xs[j % 2], out)
-        torch.cuda.synchronize()
-        dist.barrier()
-        td = tmax(_time_calls(lambda: comm.all_reduce(xs[0], out), max(5, min(args.steps, 20))))
-        default_sel.update({"ms_per_step": round(td * 1e3, 4), "algbw_GBs": round(S / td / 1e9, 2),
-                            "frac_of_assumed_ceiling": round(S / td / 1e9 / (n * XGMI_LINK_GBS / 2), 4),
-                            "correct_bitexact": check_run(default_sel["algo"], *_builtin_shape(m, n, S))
-                            if checker is not None else None})
-    except Exception as e:  # recorded, never fatal for the headline line
-        default_sel["error"] = str(e)[-300:]
+    def time_default_selector():
+        progress("default selector")
+        sel_ = {"algo": SELECT_NAMES[m.lib().mscclppAmdSelectAlgo(n, S, 0)],
+                "source": m.tuned_config_source("allreduce", n, S)}
+        try:
+            for j in range(3):
+                comm.all_reduce(xs[j % 2], out)
+            torch.cuda.synchronize()
+            dist.barrier()
+            td = tmax(_time_calls(lambda: comm.all_reduce(xs[0], out), max(5, min(args.steps, 20))))
+            sel_.update({"ms_per_step": round(td * 1e3, 4), "algbw_GBs": round(S / td / 1e9, 2),
+                         "frac_of_assumed_ceiling": round(S / td / 1e9 / (n * XGMI_LINK_GBS / 2), 4),
+                         "correct_bitexact": check_run(sel_["algo"], *_builtin_shape(m, n, S))
+                         if checker is not None else None})
+        except Exception as e:  # recorded, never fatal for the headline line
+            sel_["error"] = str(e)[-300:]
+        return sel_
+
+    default_sel = time_default_selector() if args.full else None
     # ---- pick the algorithm and launch shape (untimed; every rank tries the same candidates in the
     # same order).  Large buckets: the scratch-based all-pairs RS+AG (fullmesh, puts), the zero-copy
     # RS+AG (reads peers' inputs, writes peers' outputs) and the pipelined RS+AG -- which one drives
@@ -840,6 +880,8 @@ def bench_multi(args):
     t = tmax(t_local)
     kern_ms = tmax(ev0.elapsed_time(ev1) / args.steps)
     errc = comm.device_error()
+    if args.dump_outputs:  # every rank's result of the last timed step, before anything below launches again
+        dump_output(args.dump_outputs, f"out_rank{rank}", out, DUMP_BUDGET // world)
     bitexact = {}
     if checker is not None:
         progress("bit-exact check of the timed step and of every tuned candidate")
@@ -863,18 +905,20 @@ def bench_multi(args):
                 bitexact[f"{a}:{nbytes >> 10}KiB"] = check_run(a, 0, 0, nbytes)
             except Exception as e:  # recorded, never fatal for the headline line
                 bitexact[f"{a}:{nbytes >> 10}KiB"] = f"error: {e}"[:200]
-    phases = phase_breakdown(m, comm, n, dev, tmax, algo, nb, nt, xs[0], out)
+    phases = phase_breakdown(m, comm, n, dev, tmax, algo, nb, nt, xs[0], out) if args.full else None
     ok = errc == 0 and all(v is True for v in bitexact.values()) if bitexact else errc == 0
-    if not bitexact:  # --no-check: fp32 gloo reference with the tolerance of correctness.py:257-258
+    if not bitexact and args.full:  # --no-check: fp32 gloo reference with the tolerance of correctness.py:257-258
         ref = xs[1].float().cpu()
         dist.all_reduce(ref)
         ok = bool(torch.allclose(out.float().cpu(), ref, rtol=1e-2, atol=5e-4 * n)) and errc == 0
     algbw = S / t / 1e9
-    progress("xGMI probe")
-    try:
-        probe = xgmi_probe(comm, n, dev, tmax, dist.barrier)
-    except Exception as e:  # recorded, never fatal for the headline line
-        probe = {"error": str(e)[-300:]}
+    probe = {"error": "not measured: the xGMI probe runs with --full"}
+    if args.full:
+        progress("xGMI probe")
+        try:
+            probe = xgmi_probe(comm, n, dev, tmax, dist.barrier)
+        except Exception as e:  # recorded, never fatal for the headline line
+            probe = {"error": str(e)[-300:]}
     roofline, xgmi = multi_roofline(n, S, algo, t, kern_ms, probe, ndev < world)
     res = {
         "metric": "device-resident AllReduce algbw GB/s fp16 at 1/2/4/8 MI355X; % xGMI roofline",
@@ -905,7 +949,8 @@ def bench_multi(args):
         "roofline": roofline,
         "xgmi": xgmi,
         "tune_ms": {f"{k[0]}:{k[1]}x{k[2]}": round(v * 1e3, 4) for k, v in tune.items()},
-        "correct": ok,
+        "correct": ok if args.full else None,  # a plain run checks the device error word alone
+        "device_error": errc,
         "correct_bitexact": bitexact,
         "phases_us": phases,
     }
@@ -935,6 +980,14 @@ def bench_multi(args):
             res["tuned_config_table"] = table
     # last: on a rehearsal box (ranks sharing one device) the extra stream queues of a graph capture
     # slow every later launch of those ranks, so nothing is measured after it
+    def finish():
+        comm.destroy()
+        dist.barrier()
+        dist.destroy_process_group()
+        return res if rank == 0 else None
+
+    if not args.full:
+        return finish()
     progress("graph-captured headline")
     try:
         # common.cc:202-227: 20 calls captured in one graph, 15 graph launches, per-call time
@@ -957,10 +1010,7 @@ def bench_multi(args):
         del graph
     except Exception as e:  # recorded, never fatal for the headline line
         res["graph"] = {"error": str(e)[-300:]}
-    comm.destroy()
-    dist.barrier()
-    dist.destroy_process_group()
-    return res if rank == 0 else None
+    return finish()
 
 
 def _builtin_shape(m, n, S):

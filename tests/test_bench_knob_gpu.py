@@ -18,7 +18,7 @@ def _bench(extra_env):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(extra_env)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--algo", "fullmesh",
-                        "--bytes", str(8 << 20), "--steps", "3", "--warmup", "1", "--no-extras"],
+                        "--bytes", str(8 << 20), "--steps", "3", "--warmup", "1", "--full", "--no-extras"],
                        env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

@@ -311,6 +311,41 @@ def test_extras_check_every_timed_size():
     assert bench.ll16_ceiling(8) == pytest.approx(307.2)
 
 
+def test_plain_run_measures_the_headline_alone(monkeypatch):
+    """Without --full every baseline, extra and oracle check is off; --full turns them on, and its
+    --no-* options still take single parts out."""
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.no_cpu_baseline and a.no_extras and a.no_check and a.dump_outputs is None
+    assert a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and not (a.no_cpu_baseline or a.no_extras or a.no_check) and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-extras"])
+    a = bench.parse()
+    assert a.no_extras and not a.no_cpu_baseline
+
+
+def test_dump_output_is_float32_bounded_and_repeatable(tmp_path):
+    """--dump-outputs: a small output is written whole as float32; one above the budget is cut to
+    budget / 4 elements at the same seeded positions every time, in their order in the output."""
+    import bench
+
+    t = torch.arange(5000, dtype=torch.float32).to(torch.float16).reshape(50, 100)
+    bench.dump_output(str(tmp_path / "a"), "out", t, 1 << 20)
+    whole = np.load(tmp_path / "a" / "out.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, t.float().reshape(-1).numpy())
+    big = torch.arange(4096, dtype=torch.float32)
+    for d in ("b", "c"):
+        bench.dump_output(str(tmp_path / d), "out", big, 4000)
+    s1, s2 = np.load(tmp_path / "b" / "out.npy"), np.load(tmp_path / "c" / "out.npy")
+    assert s1.dtype == np.float32 and s1.size == 1000 and s1.nbytes <= 4000
+    assert np.array_equal(s1, s2) and np.all(np.diff(s1) > 0) and len(set(s1.tolist())) == 1000
+    assert bench.DUMP_BUDGET <= 60 * 10**6
+
+
 def test_pingpong_extras_labels():
     """The N=1 line's ping-pong extras: the two host-proxy ranks' LL16 / LL8
     latencies, labelled a shared-device figure on a 1-GPU box and one xGMI hop on a node; a failed

@@ -10,5 +10,5 @@ OUT=$ROOT/gpurun_out/prof_multi_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o bench --output-format csv -- \
-  python3 "$ROOT/bench.py" --gpus "$N" --steps 20 --warmup 5 --no-cpu-baseline --no-extras > "$OUT/bench.log" 2>&1
+  python3 "$ROOT/bench.py" --gpus "$N" --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras > "$OUT/bench.log" 2>&1
 tail -n 1 "$OUT/bench.log" > "$OUT/bench_line.json"
