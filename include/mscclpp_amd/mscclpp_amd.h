@@ -134,6 +134,10 @@ int mscclppAmdSelfReduceLL16(const void* x, const void* y, void* pkts, void* out
                              uint32_t* flags, int nblocks, uint64_t budgetTicks, uint32_t* err, void* stream);
 /* The default shape for `bytes`: waves per workgroup, KiB per wave and round, workgroups, skewed. */
 int mscclppAmdSelfReduceLL16DefaultShape(size_t bytes, int* waves, int* units, int* nblocks, int* skew);
+/* The shape mscclppAmdSelfReduceLL16 launches for `bytes` on a caller's grid (nblocks > 0; <= 0: the
+ * default): waves per workgroup, KiB per wave and round, the grid (an odd nblocks rounded up to even)
+ * and the rounds between packing a tile and consuming it.  nblocks > 1024: ncclInvalidArgument. */
+int mscclppAmdSelfReduceLL16GridShape(size_t bytes, int nblocks, int* waves, int* units, int* grid, int* skew);
 
 /* Ceiling helpers used by the benchmark.  mscclppAmdCopy is a plain streaming copy (HBM ceiling);
  * mscclppAmdCopyJobs runs njobs copies in ONE launch, blocksPerJob workgroups each (the xGMI probe:

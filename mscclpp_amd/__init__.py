@@ -127,6 +127,7 @@ def lib():
         "mscclppAmdCopyJobs": [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(sz), i32, i32, vp],
         "mscclppAmdCopyJobsPolicy": [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(sz), i32, i32, i32, i32, vp],
         "mscclppAmdSelfReduceLL16DefaultShape": [sz, vp, vp, vp, vp],
+        "mscclppAmdSelfReduceLL16GridShape": [sz, i32, vp, vp, vp, vp],
         "ncclCommSplit": [vp, i32, i32, ctypes.POINTER(vp), vp],
         "mscclppAmdBroadcastLaunch": [ctypes.POINTER(RankView), i32, i32, sz, i32, i32, i32, u64, vp],
         "ncclGetUniqueId": [ctypes.POINTER(UniqueId)],
@@ -263,6 +264,14 @@ def self_reduce_ll16(x, y, pkts_ptr, out, flags, err, op=SUM, nblocks=0, budget_
         ctypes.c_void_p(out.data_ptr()), nbytes, reduce_code(x.dtype, accum), op, ctypes.c_void_p(flags.data_ptr()),
         nblocks, budget_ticks or 200_000_000, ctypes.c_void_p(err.data_ptr()), stream_ptr(stream))
     check(code, "self_reduce_ll16")
+
+
+def self_reduce_shape(nbytes, nblocks=0):
+    """(waves, KiB per wave and round, grid, skew) self_reduce_ll16 launches for nbytes on a caller's grid."""
+    w, u, g, sk = (ctypes.c_int() for _ in range(4))
+    check(lib().mscclppAmdSelfReduceLL16GridShape(nbytes, nblocks, ctypes.byref(w), ctypes.byref(u), ctypes.byref(g),
+                                                  ctypes.byref(sk)), "self_reduce_shape")
+    return w.value, u.value, g.value, sk.value
 
 
 def tuned_config(collective, nranks, nbytes):

@@ -739,6 +739,8 @@ int launchAllReduceLL(int algo, const mscclppAmdRankView* views, int nviews, int
   if (algo == MSCCLPP_AMD_ALGO_PACKET) {
     // an explicit grid narrower than the peer count is an invalid argument (allreduce_packet.cu:238-241)
     if (nblocks > 0 && nblocks < nranks - 1) return 4;
+    // ... and so is one above the flag slots, whatever rounding it down to the peer count would leave
+    if (nblocks > kFlagSlots) return 4;
     ll16Defaults(nranks, bytes, nblocks, nthreads);
     if (nblocks > kFlagSlots || nthreads > 512 || nthreads % 64) return 4;
     LL16Geom g = ll16Geometry(nranks, bytes, dtype);

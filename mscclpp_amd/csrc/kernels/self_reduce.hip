@@ -484,6 +484,18 @@ extern "C" int mscclppAmdSelfReduceLL16DefaultShape(size_t bytes, int* waves, in
   return 0;
 }
 
+// The launch shape mscclppAmdSelfReduceLL16 takes for `bytes` on a caller's grid (nblocks <= 0: the default).
+extern "C" int mscclppAmdSelfReduceLL16GridShape(size_t bytes, int nblocks, int* waves, int* units, int* grid,
+                                                 int* skew) {
+  if (!waves || !units || !grid || !skew || nblocks > 1024) return 4;
+  const SelfReduceShape sh = selfReduceShape(bytes, nblocks);
+  *waves = sh.waves;
+  *units = sh.units;
+  *grid = sh.nblocks;
+  *skew = sh.skew;
+  return 0;
+}
+
 extern "C" int mscclppAmdCopy(const void* src, void* dst, size_t bytes, int nblocks, void* streamPtr) {
   if (!src || !dst || bytes == 0 || (bytes % 16) != 0) return 4;
   if (nblocks <= 0) nblocks = 2048;
