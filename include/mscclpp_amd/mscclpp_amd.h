@@ -176,6 +176,25 @@ int mscclppAmdAllReduceLaunch(int algo, const mscclppAmdRankView* views, int nvi
 int mscclppAmdCollectiveLaunch(int coll, int algo, const mscclppAmdRankView* views, int nviews, int nranks,
                                size_t bytes, int dtype, int op, int nblocks, int nthreads, uint64_t budgetTicks,
                                void* stream);
+/* AllToAll / AllToAllv by a zero-copy pull (kernels/alltoall.hip).  One segment per peer p, in bytes:
+ * the rank receives `len` bytes at `dstOff` of its output from `srcOff` of peer p's input
+ * (views[i].peerInput[p]; p == rank: its own input, a local copy).  Equal-split AllToAll of blocks
+ * of B bytes is srcOff = rank * B, dstOff = p * B, len = B.  Zero-length segments are skipped;
+ * segments may start at any byte (16-byte aligned starts on both sides take the fast path). */
+typedef struct {
+  uint64_t srcOff;
+  uint64_t dstOff;
+  uint64_t len;
+} mscclppAmdAllToAllSeg;
+/* Views as for mscclppAmdAllReduceLaunch (input = send buffer, output = receive buffer, peerInput[q]
+ * = rank q's send buffer; no scratch).  segs: host memory, [nviews][nranks], copied before the call
+ * returns.  nblocks <= 0: 256 KiB of the busiest view's receive bytes per workgroup, 8..128; every
+ * rank of one collective must launch the same nblocks.  With nviews > 1 the table travels through
+ * a device buffer the library allocates at the device's first such launch (not under capture).
+ * 4: a null or out-of-range argument or launch shape; 5: a workgroup's range of a segment exceeds
+ * 4 GiB (more workgroups carry it), or the grid cannot be resident at once. */
+int mscclppAmdAllToAllLaunch(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdAllToAllSeg* segs,
+                             int nblocks, int nthreads, uint64_t budgetTicks, void* stream);
 /* Scratch bytes per rank (both halves) that `algo` needs for `bytes` (0 if unsupported).  For the
  * pipelined RS+AG this is one stage at the default shape (32 x 512); a larger shape needs
  * mscclppAmdScratchRequiredShape. */
@@ -205,7 +224,8 @@ int mscclppAmdTunedConfigSource(const char* collective, int nranks, size_t bytes
 // bulk (fullmesh / rsag): 0 start, 1 reduce-scatter puts issued, 2 reduce-scatter handshake done,
 // 3 reduce + all-gather stores issued, 4 end; zero-copy: 0 start, 1 entry handshake done, 2 reduce +
 // all-gather stores issued, 3 end; LL16: 0 start, 1 step 1 (puts), 2 step 2 (reduce + broadcast),
-// 3 step 3 (unpack) done; LL8: 0 start, 1 puts issued, 2 end.  buf = NULL turns it off.  Returns 0,
+// 3 step 3 (unpack) done; LL8: 0 start, 1 puts issued, 2 end; AllToAll: 0 start, 1 entry handshake
+// done, 2 segments stored, 3 end.  buf = NULL turns it off.  Returns 0,
 // or 4 when the buffer is too small.
 #define MSCCLPP_AMD_TRACE_BYTES ((size_t)MSCCLPP_AMD_MAX_RANKS * 256 * 8 * 8)
 int mscclppAmdTraceSet(void* buf, size_t bytes);

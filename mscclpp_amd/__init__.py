@@ -35,12 +35,19 @@ MAX_CHANNELS = 256
 # ncclDataType_t / ncclRedOp_t (include/mscclpp_amd/nccl.h, values of the reference nccl.h:217-253)
 NCCL_DTYPES = {torch.float16: 6, torch.bfloat16: 9, torch.float32: 7, torch.int32: 2, torch.uint8: 1,
                torch.float8_e4m3fn: 10, torch.float8_e5m2: 11}
+# the byte-moving collectives carry every type with a size: the remaining ncclDataType_t values
+NCCL_MOVE_DTYPES = {torch.int8: 0, torch.int64: 4, torch.float64: 8}
 NCCL_OPS = {"sum": 0, "min": 3}
 DTYPE_CODES = {torch.float16: F16, torch.bfloat16: BF16, torch.float32: F32, torch.int32: I32, torch.uint8: U8,
                torch.float8_e4m3fn: E4M3, torch.float8_e5m2: E5M2}
 # accumulation dtype (ncclDataType_t) -> reduce-type code, for fp8 buffers
 ACCUM_CODES = {(torch.float8_e4m3fn, torch.float16): E4M3_ACC_F16, (torch.float8_e5m2, torch.float16): E5M2_ACC_F16,
                (torch.float8_e4m3fn, torch.float32): E4M3_ACC_F32, (torch.float8_e5m2, torch.float32): E5M2_ACC_F32}
+
+
+def nccl_dtype(dtype):
+    """ncclDataType_t of a torch dtype for a collective that only moves bytes."""
+    return NCCL_DTYPES[dtype] if dtype in NCCL_DTYPES else NCCL_MOVE_DTYPES[dtype]
 
 
 def reduce_code(dtype, accum=None):
@@ -80,6 +87,11 @@ class RankView(ctypes.Structure):
         ("peerInput", ctypes.c_void_p * MAX_RANKS),
         ("pipeSems", ctypes.c_void_p),
     ]
+
+
+class AllToAllSeg(ctypes.Structure):
+    """mscclppAmdAllToAllSeg: bytes received from one peer (srcOff in its send buffer, dstOff in the own receive buffer)."""
+    _fields_ = [("srcOff", ctypes.c_uint64), ("dstOff", ctypes.c_uint64), ("len", ctypes.c_uint64)]
 
 
 class UniqueId(ctypes.Structure):
@@ -130,6 +142,10 @@ def lib():
         "mscclppAmdSelfReduceLL16GridShape": [sz, i32, vp, vp, vp, vp],
         "ncclCommSplit": [vp, i32, i32, ctypes.POINTER(vp), vp],
         "mscclppAmdBroadcastLaunch": [ctypes.POINTER(RankView), i32, i32, sz, i32, i32, i32, u64, vp],
+        "mscclppAmdAllToAllLaunch": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(AllToAllSeg), i32, i32, u64, vp],
+        "ncclAllToAll": [vp, vp, sz, i32, vp, vp],
+        "ncclAllToAllv": [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp, ctypes.POINTER(sz), ctypes.POINTER(sz), i32, vp,
+                          vp],
         "ncclGetUniqueId": [ctypes.POINTER(UniqueId)],
         "ncclCommInitRank": [ctypes.POINTER(vp), i32, UniqueId, i32],
         "ncclCommDestroy": [vp],
@@ -308,6 +324,7 @@ TRACE_PHASES = {
     "rsag_zc": ("entry_handshake", "reduce_ag", "exit_handshake"),
     "packet": ("step1_put", "step2_reduce_bcast", "step3_unpack"),
     "allpair": ("put", "reduce"),
+    "alltoall": ("entry_handshake", "pull", "exit_handshake"),
 }
 
 
@@ -439,6 +456,22 @@ class InProcessRanks:
                                                stream_ptr(stream))
         check(code, "in-process broadcast")
 
+    def all_to_all(self, sends, recvs, segs=None, nblocks=0, nthreads=0, budget_ticks=500_000_000, stream=None):
+        """ncclAllToAll(v) for in-process ranks.  segs[r][p] = (src_off, dst_off, nbytes): rank r receives
+        nbytes at byte dst_off of recvs[r] from byte src_off of sends[p].  None: the equal split of
+        sends[0] (block p of sends[q] lands as block q of recvs[p])."""
+        n = self.n
+        if segs is None:
+            blk = sends[0].numel() * sends[0].element_size() // n
+            segs = [[(r * blk, p * blk, blk) for p in range(n)] for r in range(n)]
+        tab = (AllToAllSeg * (n * n))()
+        for r in range(n):
+            for p in range(n):
+                tab[r * n + p] = AllToAllSeg(*segs[r][p])
+        arr = self.views(sends, recvs)
+        code = lib().mscclppAmdAllToAllLaunch(arr, n, n, tab, nblocks, nthreads, budget_ticks, stream_ptr(stream))
+        check(code, "in-process all_to_all")
+
     def errors(self):
         return [int(e[0].item()) for e in self.err]
 
@@ -527,6 +560,22 @@ class Communicator:
         recv = send if recv is None else recv
         check(lib().ncclBroadcast(ctypes.c_void_p(send.data_ptr()), ctypes.c_void_p(recv.data_ptr()), recv.numel(),
                                   NCCL_DTYPES[recv.dtype], root, self.comm, stream_ptr(stream)), "ncclBroadcast")
+        return recv
+
+    def all_to_all(self, send, recv, stream=None):
+        """ncclAllToAll(send, recv, count, dtype, comm, stream): block p of send lands as block rank of
+        rank p's recv; count = elements per block.  Any dtype is carried (a byte move)."""
+        check(lib().ncclAllToAll(ctypes.c_void_p(send.data_ptr()), ctypes.c_void_p(recv.data_ptr()),
+                                 send.numel() // self.nranks, nccl_dtype(send.dtype), self.comm, stream_ptr(stream)),
+              "ncclAllToAll")
+        return recv
+
+    def all_to_all_v(self, send, send_counts, send_displs, recv, recv_counts, recv_displs, stream=None):
+        """ncclAllToAllv: counts and displacements in elements, one per rank."""
+        arr = lambda xs: (ctypes.c_size_t * self.nranks)(*xs)
+        check(lib().ncclAllToAllv(ctypes.c_void_p(send.data_ptr()), arr(send_counts), arr(send_displs),
+                                  ctypes.c_void_p(recv.data_ptr()), arr(recv_counts), arr(recv_displs),
+                                  nccl_dtype(send.dtype), self.comm, stream_ptr(stream)), "ncclAllToAllv")
         return recv
 
     def register_buffer(self, t):

@@ -596,7 +596,7 @@ int mscclppAmdCommRegistrationStats(ncclComm_t comm, size_t* userRegistrations, 
                                     size_t* retiredMappings) {
   if (!comm) return ncclInvalidArgument;
   std::lock_guard<std::mutex> lk(comm->mu);
-  if (userRegistrations) *userRegistrations = comm->userRegs.size();
+  if (userRegistrations) *userRegistrations = comm->userRegs.size() + comm->pairedRegs.size();
   if (liveMappings) *liveMappings = liveIpcMappings();
   if (retiredMappings) {  // mappings still waiting for their last launches to complete
     comm->flushRetired();

@@ -32,6 +32,9 @@ int launchAllReducePipeline(const mscclppAmdRankView* views, int nviews, int nra
                             int nblocks, int nthreads, uint64_t budget, hipStream_t s);
 int launchBroadcast(const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes, int root, int nblocks,
                     int nthreads, uint64_t budget, hipStream_t s);
+int launchAllToAll(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdAllToAllSeg* segs,
+                   int nblocks, int nthreads, uint64_t budget, hipStream_t s);
+int alltoallDefaultBlocks(uint64_t maxRecvBytes);
 size_t ll16ScratchRequired(int nranks, size_t bytes, int dtype);
 size_t ll8ScratchRequired(int nranks, size_t bytes, int dtype);
 size_t testLLScratchRequired(int nranks, size_t bytes);
@@ -551,6 +554,8 @@ struct ncclComm {
     PeerBufs bases;
     UseEvents uses;
     std::map<uint64_t, std::array<void*, MSCCLPP_AMD_MAX_RANKS>> byOffset;
+    // (allocation base, HIP buffer id) of every rank's buffer this one was exchanged with (pairedRegs)
+    std::array<std::pair<uint64_t, uint64_t>, MSCCLPP_AMD_MAX_RANKS> peerIdent{};
   };
   std::map<std::pair<uint64_t, uint64_t>, UserReg> userRegs;
   uint64_t useClock = 0;
@@ -558,7 +563,9 @@ struct ncclComm {
   // host all-gathers the registration path made: allocations exchanged, offsets exchanged
   uint64_t allocExchanges = 0, offsetExchanges = 0;
 
-  void retireReg(std::map<std::pair<uint64_t, uint64_t>, UserReg>::iterator it) {
+  typedef std::map<std::pair<uint64_t, uint64_t>, UserReg> RegMap;
+  void retireReg(RegMap::iterator it) { retireReg(it, userRegs); }
+  void retireReg(RegMap::iterator it, RegMap& regs) {
     if (it->second.pinned)
       info("rank " + std::to_string(rank) + ": pinned registration of allocation " +
            std::to_string(it->first.first) + " retired (its address now belongs to a new allocation)");
@@ -569,7 +576,18 @@ struct ncclComm {
     for (auto t = touched.begin(); t != touched.end();)  // not recorded for a launch any more
       t = *t == &it->second.uses ? touched.erase(t) : t + 1;
     if (!r.maps.empty() || !r.uses.ev.empty()) retired.push_back(std::move(r));
-    userRegs.erase(it);
+    regs.erase(it);
+  }
+
+  // The least recently used unpinned registration of `regs` goes when kMaxUserRegs unpinned ones are held.
+  void evictFor(RegMap& regs) {
+    size_t unpinned = 0;
+    for (const auto& e : regs) unpinned += e.second.pinned ? 0 : 1;
+    if (unpinned < kMaxUserRegs) return;
+    auto lru = regs.end();
+    for (auto j = regs.begin(); j != regs.end(); ++j)
+      if (!j->second.pinned && (lru == regs.end() || j->second.lastUse < lru->second.lastUse)) lru = j;
+    retireReg(lru, regs);
   }
 
   std::array<void*, MSCCLPP_AMD_MAX_RANKS> registerOutput(void* out, hipStream_t stream = nullptr, bool pin = false) {
@@ -584,14 +602,7 @@ struct ncclComm {
       it = userRegs.end();
     }
     if (it == userRegs.end()) {
-      size_t unpinned = 0;
-      for (const auto& e : userRegs) unpinned += e.second.pinned ? 0 : 1;
-      if (unpinned >= kMaxUserRegs) {
-        auto lru = userRegs.end();
-        for (auto j = userRegs.begin(); j != userRegs.end(); ++j)
-          if (!j->second.pinned && (lru == userRegs.end() || j->second.lastUse < lru->second.lastUse)) lru = j;
-        retireReg(lru);
-      }
+      evictFor(userRegs);
       UserReg reg;
       reg.bufferId = bid;
       reg.bases = exchange(base);  // collective: every rank registers its matching buffer now
@@ -672,12 +683,106 @@ struct ncclComm {
   std::array<bool, MSCCLPP_AMD_MAX_RANKS> bcastCaptured{};  // bcastMaps[root] used under capture
   std::vector<std::shared_ptr<void>> bcastPinned;             // replaced, but a graph may read them
 
+  // AllToAll(v) by a zero-copy pull (kernels/alltoall.hip): segs[p] = what this rank receives from
+  // rank p, in bytes.  The send buffer is what the peers read, so it is the one registered
+  // (collective on first use, cached per allocation, pinned under capture); every store goes to this
+  // rank's own receive buffer, which needs no registration.  nblocks: the same on every rank.
+  // idents: every rank's sendIdent of this call where the caller gathered them (AllToAllv,
+  // registerPaired); null: registerOutput, the other collectives' contract of matching buffers.
+  struct SendIdent;
+  int allToAll(const void* send, void* recv, const mscclppAmdAllToAllSeg* segs, int nblocks, hipStream_t stream,
+               const SendIdent* idents = nullptr) {
+    std::lock_guard<std::mutex> lk(mu);
+    touched.clear();
+    mscclppAmdRankView v = baseView(send, recv);
+    const auto ins = idents ? registerPaired(const_cast<void*>(send), idents, stream)
+                            : registerOutput(const_cast<void*>(send), stream);
+    for (int r = 0; r < nranks; ++r) v.peerInput[r] = ins[r];
+    const int rc = launchAllToAll(&v, 1, nranks, segs, nblocks, 0, spinBudgetTicks(), stream);
+    recordUses(stream);
+    return rc;
+  }
+
+  // AllToAllv's send buffers.  Its ranks pass buffers of different sizes, which each rank's
+  // allocator places on its own, so "my buffer X goes with your buffer Y" -- what userRegs caches,
+  // keyed by the local buffer alone -- does not hold from one call to the next.  The call's own
+  // all-gather therefore carries each rank's allocation identity (base, HIP buffer id), its offset
+  // and the identities its cached registration was made with (sendIdent); from the gathered rows
+  // every rank derives the same answer to "does any rank hold a pairing that is not the current
+  // one", and if so all exchange their allocations again (registerPaired).  Offsets come from the
+  // gather on every call.  These registrations live in a map of their own: re-pairing one must not
+  // touch what the matching-buffer collectives cached for the same allocation.
+  struct SendIdent {
+    uint64_t base, id, off;
+    uint64_t pairedBase[MSCCLPP_AMD_MAX_RANKS], pairedId[MSCCLPP_AMD_MAX_RANKS];
+  };
+  RegMap pairedRegs;
+
+  SendIdent sendIdent(const void* send) {
+    void* base = nullptr;
+    size_t sz = 0;
+    HIPCHECK(hipMemGetAddressRange((hipDeviceptr_t*)&base, &sz, (hipDeviceptr_t)send));
+    SendIdent s{};
+    s.base = (uint64_t)base;
+    s.id = allocationId(base);
+    s.off = (uint64_t)((const char*)send - (char*)base);
+    auto it = pairedRegs.find(std::make_pair((uint64_t)base, (uint64_t)sz));
+    if (it != pairedRegs.end() && it->second.bufferId == s.id)
+      for (int r = 0; r < nranks; ++r) {
+        s.pairedBase[r] = it->second.peerIdent[(size_t)r].first;
+        s.pairedId[r] = it->second.peerIdent[(size_t)r].second;
+      }
+    return s;
+  }
+
+  // True when rank q's cached pairing (row q of the gathered idents) is not the current buffers.
+  static bool pairingStale(const SendIdent* all, int n, int q) {
+    for (int r = 0; r < n; ++r)
+      if (r != q && (all[q].pairedBase[r] != all[r].base || all[q].pairedId[r] != all[r].id || !all[r].id)) return true;
+    return false;
+  }
+
+  // all: every rank's sendIdent of this call; collective exactly when any rank's pairing is stale.
+  std::array<void*, MSCCLPP_AMD_MAX_RANKS> registerPaired(void* send, const SendIdent* all, hipStream_t stream) {
+    bool reexchange = false;
+    for (int q = 0; q < nranks; ++q) reexchange = reexchange || pairingStale(all, nranks, q);
+    const SendIdent& me = all[rank];
+    size_t sz = 0;
+    void* base = nullptr;
+    HIPCHECK(hipMemGetAddressRange((hipDeviceptr_t*)&base, &sz, (hipDeviceptr_t)send));
+    const auto key = std::make_pair(me.base, (uint64_t)sz);
+    auto it = pairedRegs.find(key);
+    if (it != pairedRegs.end() && (reexchange || it->second.bufferId != me.id)) {
+      retireReg(it, pairedRegs);  // (an unchanged peer's mapping is found open again at its address)
+      it = pairedRegs.end();
+    }
+    if (it == pairedRegs.end()) {
+      if (!reexchange) throw std::logic_error("AllToAllv registration out of step");
+      evictFor(pairedRegs);
+      UserReg reg;
+      reg.bufferId = me.id;
+      reg.bases = exchange(base);
+      ++allocExchanges;
+      for (int r = 0; r < nranks; ++r) reg.peerIdent[(size_t)r] = std::make_pair(all[r].base, all[r].id);
+      it = pairedRegs.emplace(key, std::move(reg)).first;
+    }
+    UserReg& reg = it->second;
+    reg.lastUse = ++useClock;
+    if (capturing(stream)) reg.pinned = true;
+    std::array<void*, MSCCLPP_AMD_MAX_RANKS> res{};
+    for (int r = 0; r < nranks; ++r) res[r] = r == rank ? send : (char*)reg.bases[r] + all[r].off;
+    touched.push_back(&reg.uses);
+    flushRetired();
+    return res;
+  }
+
   // Drop every cached mapping of peers' user buffers (collective).  Scratch, token and flag
   // mappings stay.  After this, the next use of any buffer registers it afresh.
   void dropUserRegistrations() {
     HIPCHECK(hipDeviceSynchronize());
     boot->barrier();  // no rank still runs a kernel that uses a mapping being closed
     while (!userRegs.empty()) retireReg(userRegs.begin());
+    while (!pairedRegs.empty()) retireReg(pairedRegs.begin(), pairedRegs);
     for (auto& m : bcastMaps) m.reset();
     for (auto& u : bcastUses)
       for (auto& e : u.ev) (void)hipEventDestroy(e.second);
@@ -849,6 +954,9 @@ struct ncclComm {
     for (auto& kv : userRegs)
       for (auto& e : kv.second.uses.ev) (void)hipEventDestroy(e.second);
     userRegs.clear();
+    for (auto& kv : pairedRegs)
+      for (auto& e : kv.second.uses.ev) (void)hipEventDestroy(e.second);
+    pairedRegs.clear();
     touched.clear();
     for (auto& m : bcastMaps) m.reset();
     for (auto& u : bcastUses)
@@ -903,7 +1011,7 @@ struct VendorNccl {
 // The vendor library named by MSCCLPP_AMD_NCCL_LIB_PATH (or MSCCLPP_NCCL_LIB_PATH), or null.
 const VendorNccl* vendorNccl();
 // MSCCLPP_AMD_FORCE_NCCL_FALLBACK_OPERATION ("all" or a comma list of allreduce, allgather,
-// reducescatter, broadcast) names `op`.
+// reducescatter, broadcast, alltoall, alltoallv) names `op`.
 bool forcedFallback(const char* op);
 // ncclCommInitRank with the bootstrap's connect / receive timeout given (ncclCommInitRank takes it
 // from MSCCLPP_AMD_BOOTSTRAP_TIMEOUT_S); commId is the 128-byte unique id.  Returns an ncclResult_t.

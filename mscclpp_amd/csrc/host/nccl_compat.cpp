@@ -1,18 +1,19 @@
 // The rest of the NCCL ABI surface a framework binds (the symbols libtorch_hip.so imports), so that
 // libmscclpp_amd.so can stand in for librccl.so under LD_PRELOAD / LD_AUDIT:
 //
-//  * native here: ncclBroadcast / ncclBcast (zero-copy pull from the root), ncclCommSplit
-//    (nccl.cc:405-435), ncclCommInitRankScalable with one id, ncclCommRegister / Deregister and
-//    ncclCommWindowRegister / Deregister (the path registers buffers lazily on first use, so these
-//    only hand the pointer back);
+//  * native here: ncclBroadcast / ncclBcast (zero-copy pull from the root), ncclAllToAll /
+//    ncclAllToAllv (zero-copy pull from every peer, kernels/alltoall.hip; the reference leaves both
+//    to the vendor library, nccl.cc:794-821), ncclCommSplit (nccl.cc:405-435),
+//    ncclCommInitRankScalable with one id, ncclCommRegister / Deregister and ncclCommWindowRegister /
+//    Deregister (the path registers buffers lazily on first use, so these only hand the pointer back);
 //  * forwarded to the vendor library when MSCCLPP_AMD_NCCL_LIB_PATH (or the reference's
 //    MSCCLPP_NCCL_LIB_PATH) names it -- the reference's dlopen fallback, nccl.cc:72-160, :323-346:
-//    ncclReduce, ncclSend/Recv, ncclAllToAll(v), ncclRedOpCreatePreMulSum/Destroy,
-//    ncclGroupSimulateEnd, group calls, and AllReduce / AllGather / ReduceScatter / Broadcast for
-//    data types and operations this path does not carry or that
-//    MSCCLPP_AMD_FORCE_NCCL_FALLBACK_OPERATION (reference: MSCCLPP_FORCE_NCCL_FALLBACK_OPERATION,
-//    "all" or a comma list) forces there.  Without a vendor library they return ncclInternalError,
-//    as the reference does for the same cases.
+//    ncclReduce, ncclSend/Recv, ncclRedOpCreatePreMulSum/Destroy, ncclGroupSimulateEnd, group calls,
+//    and AllReduce / AllGather / ReduceScatter / Broadcast / AllToAll(v) for data types and
+//    operations this path does not carry or that MSCCLPP_AMD_FORCE_NCCL_FALLBACK_OPERATION
+//    (reference: MSCCLPP_FORCE_NCCL_FALLBACK_OPERATION, "all" or a comma list; keys alltoall and
+//    alltoallv for the two above) forces there.  Without a vendor library the operations not
+//    carried here return ncclInternalError, as the reference does for the same cases.
 #include <dlfcn.h>
 #include <sys/stat.h>
 
@@ -142,6 +143,11 @@ static ncclResult_t unavailable(const char* what) {
   return ncclInternalError;
 }
 
+static bool rangesOverlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + nb && y < x + na;
+}
+
 extern "C" {
 
 ncclResult_t ncclBroadcast(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, int root,
@@ -250,9 +256,20 @@ ncclResult_t ncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, nc
         HIPCHECK(hipMemcpyAsync(recvbuff, sendbuff, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
       return (int)ncclSuccess;
     }
-    if (vendorComm(comm) && vendorNccl()->AllToAll)
+    // a byte move: any data type with a size is carried.  In place is not defined for AllToAll,
+    // and a pull would race with the peers' reads
+    const size_t n = (size_t)comm->nranks, bytes = count * ncclTypeBytes(datatype);
+    if (!sendbuff || !recvbuff || bytes == 0) return (int)ncclInvalidArgument;
+    if (rangesOverlap(sendbuff, n * bytes, recvbuff, n * bytes)) {
+      warn("ncclAllToAll: the send and receive buffers overlap");
+      return (int)ncclInvalidArgument;
+    }
+    if (vendorComm(comm) && vendorNccl()->AllToAll && forcedFallback("alltoall"))
       return (int)vendorNccl()->AllToAll(sendbuff, recvbuff, count, datatype, vendorComm(comm), stream);
-    return (int)unavailable("ncclAllToAll");
+    mscclppAmdAllToAllSeg segs[MSCCLPP_AMD_MAX_RANKS];
+    for (size_t p = 0; p < n; ++p) segs[p] = {(uint64_t)comm->rank * bytes, p * bytes, bytes};
+    return comm->allToAll(sendbuff, recvbuff, segs, mscclpp_amd::alltoallDefaultBlocks(n * bytes),
+                          (hipStream_t)stream);
   });
 }
 
@@ -260,20 +277,96 @@ ncclResult_t ncclAllToAllv(const void* sendbuff, const size_t sendcounts[], cons
                            const size_t recvcounts[], const size_t rdispls[], ncclDataType_t datatype, ncclComm_t comm,
                            void* stream) {
   if (!comm) return ncclInvalidArgument;
-  if (comm->nranks == 1) {  // nccl.cc:812-818: block 0 to block 0
-    return (ncclResult_t)guarded([&] {
+  return (ncclResult_t)guarded([&] {
+    const size_t tb = ncclTypeBytes(datatype);
+    if (comm->nranks == 1) {  // nccl.cc:812-818: block 0 to block 0
       if (!recvcounts || !sdispls || !rdispls) return (int)ncclInvalidArgument;
-      const size_t tb = ncclTypeBytes(datatype), bytes = recvcounts[0] * tb;
+      const size_t bytes = recvcounts[0] * tb;
       if (bytes)
         HIPCHECK(hipMemcpyAsync((char*)recvbuff + rdispls[0] * tb, (const char*)sendbuff + sdispls[0] * tb, bytes,
                                 hipMemcpyDeviceToDevice, (hipStream_t)stream));
       return (int)ncclSuccess;
-    });
-  }
-  if (vendorComm(comm) && vendorNccl()->AllToAllv)
-    return vendorNccl()->AllToAllv(sendbuff, sendcounts, sdispls, recvbuff, recvcounts, rdispls, datatype,
-                                   vendorComm(comm), stream);
-  return unavailable("ncclAllToAllv");
+    }
+    if (vendorComm(comm) && vendorNccl()->AllToAllv && forcedFallback("alltoallv"))
+      return (int)vendorNccl()->AllToAllv(sendbuff, sendcounts, sdispls, recvbuff, recvcounts, rdispls, datatype,
+                                          vendorComm(comm), stream);
+    // A pull reads peer p's segment at p's sdispls[rank], which lives on p's host: every rank
+    // all-gathers its counts and send displacements (elements) on each call, as broadcast() gathers
+    // its handles.  Every rank then checks the WHOLE matrix and its peers' own argument checks, so
+    // all ranks return the same answer and none launches a kernel that would wait for one that
+    // refused.
+    const int n = comm->nranks, me = comm->rank;
+    // The row also carries the identity of this rank's send buffer and of the buffers its cached
+    // registration was made with (ncclComm::sendIdent): AllToAllv's buffers differ in size between
+    // ranks, so which buffer goes with which is settled per call, by every rank from the same rows.
+    struct Row {
+      uint64_t ok;
+      ncclComm::SendIdent ident;
+      uint64_t send[MSCCLPP_AMD_MAX_RANKS], sdis[MSCCLPP_AMD_MAX_RANKS], recv[MSCCLPP_AMD_MAX_RANKS];
+    };
+    Row mine{};
+    mine.ok = sendbuff && recvbuff && sendcounts && sdispls && recvcounts && rdispls && tb;
+    if (mine.ok) {
+      try {
+        std::lock_guard<std::mutex> lk(comm->mu);
+        mine.ident = comm->sendIdent(sendbuff);
+      } catch (const std::exception& e) {  // not device memory: still take part in the gather below
+        warn(std::string("ncclAllToAllv: ") + e.what());
+        (void)hipGetLastError();
+        mine.ok = 0;
+      }
+    }
+    if (mine.ok) {
+      uint64_t sLo = ~0ull, sHi = 0, rLo = ~0ull, rHi = 0;
+      for (int p = 0; p < n; ++p) {
+        mine.send[p] = sendcounts[p];
+        mine.sdis[p] = sdispls[p];
+        mine.recv[p] = recvcounts[p];
+        if (sendcounts[p]) {
+          sLo = std::min<uint64_t>(sLo, sdispls[p] * tb);
+          sHi = std::max<uint64_t>(sHi, (sdispls[p] + sendcounts[p]) * tb);
+        }
+        if (recvcounts[p]) {
+          rLo = std::min<uint64_t>(rLo, rdispls[p] * tb);
+          rHi = std::max<uint64_t>(rHi, (rdispls[p] + recvcounts[p]) * tb);
+        }
+      }
+      if (sLo < sHi && rLo < rHi &&
+          rangesOverlap((const char*)sendbuff + sLo, sHi - sLo, (const char*)recvbuff + rLo, rHi - rLo)) {
+        warn("ncclAllToAllv: the send and receive ranges overlap");
+        mine.ok = 0;
+      }
+    }
+    std::vector<Row> all((size_t)n);
+    {
+      std::lock_guard<std::mutex> lk(comm->mu);
+      comm->boot->allGather(&mine, all.data(), sizeof(Row));
+    }
+    uint64_t mostRecv = 0;
+    for (int r = 0; r < n; ++r) {
+      if (!all[(size_t)r].ok) {
+        warn("ncclAllToAllv: rank " + std::to_string(r) + " passed invalid arguments");
+        return (int)ncclInvalidArgument;
+      }
+      uint64_t sum = 0;
+      for (int p = 0; p < n; ++p) {
+        if (all[(size_t)r].recv[p] != all[(size_t)p].send[r]) {
+          warn("ncclAllToAllv: rank " + std::to_string(r) + " expects " + std::to_string(all[(size_t)r].recv[p]) +
+               " elements from rank " + std::to_string(p) + ", which sends " + std::to_string(all[(size_t)p].send[r]));
+          return (int)ncclInvalidArgument;
+        }
+        sum += all[(size_t)r].recv[p] * tb;
+      }
+      mostRecv = std::max(mostRecv, sum);
+    }
+    mscclppAmdAllToAllSeg segs[MSCCLPP_AMD_MAX_RANKS];
+    for (int p = 0; p < n; ++p)
+      segs[p] = {all[(size_t)p].sdis[me] * tb, (uint64_t)rdispls[p] * tb, (uint64_t)recvcounts[p] * tb};
+    ncclComm::SendIdent idents[MSCCLPP_AMD_MAX_RANKS];
+    for (int r = 0; r < n; ++r) idents[r] = all[(size_t)r].ident;
+    return comm->allToAll(sendbuff, recvbuff, segs, mscclpp_amd::alltoallDefaultBlocks(mostRecv), (hipStream_t)stream,
+                          idents);
+  });
 }
 
 ncclResult_t ncclRedOpCreatePreMulSum(ncclRedOp_t* op, void* scalar, ncclDataType_t datatype,
@@ -357,6 +450,24 @@ int mscclppAmdBroadcastLaunch(const mscclppAmdRankView* views, int nviews, int n
     }
     return mscclpp_amd::launchBroadcast(views, nviews, nranks, bytes, root, nblocks, nthreads,
                                         budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream);
+  });
+}
+
+// AllToAll(v) for in-process ranks: views as above, peerInput[q] = rank q's send buffer.
+int mscclppAmdAllToAllLaunch(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdAllToAllSeg* segs,
+                             int nblocks, int nthreads, uint64_t budgetTicks, void* stream) {
+  return guarded([&] {
+    if (!views || !segs || nviews < 1 || nranks < 2 || nranks > MSCCLPP_AMD_MAX_RANKS) return (int)ncclInvalidArgument;
+    if (nviews != 1 && nviews != nranks) return (int)ncclInvalidArgument;
+    for (int i = 0; i < nviews; ++i) {
+      const mscclppAmdRankView& v = views[i];
+      if (!v.input || !v.output || !v.tokens || !v.expected || !v.err) return (int)ncclInvalidArgument;
+      if (v.rank < 0 || v.rank >= nranks) return (int)ncclInvalidArgument;
+      for (int q = 0; q < nranks; ++q)
+        if (!v.peerTokens[q] || !v.peerInput[q]) return (int)ncclInvalidArgument;
+    }
+    return mscclpp_amd::launchAllToAll(views, nviews, nranks, segs, nblocks, nthreads,
+                                       budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream);
   });
 }
 

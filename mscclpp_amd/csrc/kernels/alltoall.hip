@@ -1,0 +1,229 @@
+// ncclAllToAll / ncclAllToAllv: a zero-copy pull over xGMI.
+//
+// The reference leaves both to the vendor library (nccl.cc:794-821 is a TODO; the alltoall kernels
+// of test/mscclpp-test/alltoall_test.cu are compiled for CUDA only), so this is no restatement.
+//
+// Rank r's receive segment from peer p is read straight out of p's send buffer (system-scope
+// 16-byte buffer loads, as broadcastKernel reads the root) and stored into r's own receive buffer
+// with plain stores: every store is local, nothing is written into a peer's user buffer (DESIGN.md
+// §5: remote plain / nt stores into user buffers went stale).  A table of n segments {srcOff into
+// peer p's send buffer, dstOff into the own receive buffer, len}, in bytes, drives the kernel;
+// equal-split AllToAll is the table srcOff = rank * B, dstOff = p * B, len = B.
+//
+//  * Entry handshake per workgroup (channel = blockIdx.x): the peers' send buffers are final (their
+//    producers ran earlier on the peers' streams) and this rank's earlier stream work on its receive
+//    buffer is over.
+//  * Workgroup b owns the sub-range [b * blk_p, (b + 1) * blk_p) of every segment p, blk_p =
+//    ceil(len_p / nblocks) rounded up to 16, and visits the n segments starting at a peer rotated
+//    by rank and workgroup index, so one rank's workgroups are spread over all links at any moment
+//    and the ranks do not all read the same source at once.
+//  * Exit handshake: no peer still reads this rank's send buffer when its kernel ends.  Every
+//    workgroup takes both handshakes, also one whose sub-ranges are all empty.
+//  * A sub-range whose source and destination both start 16-byte aligned moves in 16-byte units, U
+//    loads in flight per lane before their stores; any other one moves at the widest power of two
+//    (1, 2, 4, 8 bytes) dividing both addresses -- correct, not fast.  Tails move byte by byte: no
+//    byte outside [dstOff, dstOff + len) is written and none outside the source segment is read.
+#include <mutex>
+
+#include "common.hpp"
+#include "handshake.hpp"
+
+namespace mscclpp_amd {
+
+typedef mscclppAmdAllToAllSeg A2ASeg;
+
+// The segment table of a launch: by value for the one-view (one rank per process) launch -- nothing
+// to copy, and a captured graph keeps it in the kernel node -- and through a device buffer
+// ([view][kMaxRanks]) for the in-process launch, whose 8 views leave no room for 64 entries in the
+// 4 KiB of kernel arguments.
+template <int NV>
+struct A2ASegs {
+  const A2ASeg* tab;
+  __device__ __forceinline__ A2ASeg at(int view, int p) const { return tab[view * kMaxRanks + p]; }
+};
+template <>
+struct A2ASegs<1> {
+  A2ASeg s[kMaxRanks];
+  __device__ __forceinline__ A2ASeg at(int, int p) const { return s[p]; }
+};
+
+template <int NV>
+struct A2AArgs {
+  Views<NV> views;
+  A2ASegs<NV> segs;
+  uint64_t budget;
+  uint64_t* trace;  // phase stamps: 0 start, 1 entry handshake done, 2 segments stored, 3 end
+  int nranks;
+  int pad;
+};
+struct A2ATableArg {
+  A2ASeg s[kMaxRanks * kMaxRanks];
+};
+constexpr size_t kKernargLimit = 4096;
+static_assert(sizeof(mscclppAmdRankView) == 336, "Views<kMaxRanks> is sized against the kernel-argument limit");
+static_assert(sizeof(A2AArgs<1>) <= kKernargLimit, "one-view AllToAll arguments exceed the kernel-argument limit");
+static_assert(sizeof(A2AArgs<kMaxRanks>) <= kKernargLimit, "in-process AllToAll arguments exceed the kernel-argument limit");
+static_assert(sizeof(A2ATableArg) + 16 <= kKernargLimit, "the staged segment table exceeds the kernel-argument limit");
+
+template <int Policy, int W>
+__device__ __forceinline__ void copy_narrow(const uint8_t* src, uint8_t* dst, uint64_t nUnits, uint32_t tid, uint32_t T) {
+  const auto rs = make_rsrc(src);
+  const auto rd = make_rsrc(dst);
+  for (uint64_t u = tid; u < nUnits; u += T) {  // (64-bit: nUnits may sit within T of 2^32)
+    const uint32_t off = (uint32_t)(u * W);
+    if constexpr (W == 8)
+      store8<kPlain>(rd, off, load8<Policy>(rs, off));
+    else if constexpr (W == 4)
+      store4<kPlain>(rd, off, load4<Policy>(rs, off));
+    else if constexpr (W == 2)
+      __builtin_amdgcn_raw_buffer_store_b16(__builtin_amdgcn_raw_buffer_load_b16(rs, off, 0, Policy), rd, off, 0, kPlain);
+    else
+      __builtin_amdgcn_raw_buffer_store_b8(__builtin_amdgcn_raw_buffer_load_b8(rs, off, 0, Policy), rd, off, 0, kPlain);
+  }
+}
+
+// dst[0, len) = src[0, len); len <= kBlkOffsetLimit (one buffer resource each, rebased here).
+template <int Policy, int U>
+__device__ __forceinline__ void copy_range(const uint8_t* src, uint8_t* dst, uint64_t len, uint32_t tid, uint32_t T) {
+  const uint32_t mis = ((uint32_t)(uintptr_t)src | (uint32_t)(uintptr_t)dst) & 15u;
+  uint64_t done;
+  if (mis == 0) {
+    const auto rs = make_rsrc(src);
+    const auto rd = make_rsrc(dst);
+    const uint32_t nUnits = (uint32_t)(len / 16);
+    for (uint32_t u0 = tid; u0 < nUnits; u0 += T * U) {
+      u32x4 w[U];
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        const uint32_t u = u0 + k * T;
+        if (u < nUnits) w[k] = load16<Policy>(rs, u * 16u);
+      }
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        const uint32_t u = u0 + k * T;
+        if (u < nUnits) store16<kPlain>(rd, u * 16u, w[k]);
+      }
+    }
+    done = (uint64_t)nUnits * 16;
+  } else if (mis & 1u) {
+    done = 0;
+  } else if (mis & 2u) {
+    copy_narrow<Policy, 2>(src, dst, len / 2, tid, T);
+    done = len & ~1ull;
+  } else if (mis & 4u) {
+    copy_narrow<Policy, 4>(src, dst, len / 4, tid, T);
+    done = len & ~3ull;
+  } else {
+    copy_narrow<Policy, 8>(src, dst, len / 8, tid, T);
+    done = len & ~7ull;
+  }
+  if (done < len) copy_narrow<Policy, 1>(src + done, dst + done, len - done, tid, T);
+}
+
+template <int NV, int U>
+__global__ void __launch_bounds__(512) alltoallKernel(A2AArgs<NV> a) {
+  const int vi = NV == 1 ? 0 : (int)blockIdx.y;
+  const mscclppAmdRankView& v = a.views.v[vi];
+  const int rank = v.rank, n = a.nranks;
+  const uint32_t T = blockDim.x, tid = threadIdx.x, b = blockIdx.x, nb = gridDim.x;
+  trace_stamp(a.trace, 0);
+  block_handshake(v, n, rank, b, a.budget);
+  trace_stamp(a.trace, 1);
+#pragma unroll 1
+  for (int s = 0; s < n; ++s) {
+    const int p = (int)(((uint32_t)(rank + 1 + s) + b) % (uint32_t)n);
+    const A2ASeg seg = a.segs.at(vi, p);
+    const uint64_t blk = ((seg.len + nb - 1) / nb + 15) & ~15ull;
+    const uint64_t bOff = (uint64_t)b * blk;
+    if (bOff >= seg.len) continue;
+    const uint64_t len = seg.len - bOff < blk ? seg.len - bOff : blk;
+    uint8_t* dst = (uint8_t*)v.output + seg.dstOff + bOff;
+    if (p == rank)
+      copy_range<kPlain, U>((const uint8_t*)v.input + seg.srcOff + bOff, dst, len, tid, T);
+    else
+      copy_range<kSystem, U>((const uint8_t*)v.peerInput[p] + seg.srcOff + bOff, dst, len, tid, T);
+  }
+  trace_stamp(a.trace, 2);
+  block_handshake(v, n, rank, b, a.budget);
+  trace_stamp(a.trace, 3);
+}
+
+__global__ void alltoallTableKernel(A2ATableArg t, A2ASeg* dst) {
+  if (threadIdx.x < kMaxRanks * kMaxRanks) dst[threadIdx.x] = t.s[threadIdx.x];
+}
+
+constexpr uint64_t kBlkOffsetLimit = 0xFFFFFFFFull - 64;  // as launchBroadcast: one descriptor per workgroup range
+
+// 256 KiB of the busiest rank's receive bytes per workgroup, 8..128 workgroups.  Every rank of a
+// collective must launch the same grid (workgroup b hand-shakes with the peers' workgroup b), so a
+// caller with one view passes the shape it derived from what every rank knows.
+int alltoallDefaultBlocks(uint64_t maxRecvBytes) {
+  const uint64_t want = (maxRecvBytes + (256u << 10) - 1) / (256u << 10);
+  return (int)(want < 8 ? 8 : want > 128 ? 128 : want);
+}
+
+// Device copies of the in-process launches' tables: a ring of slots per device, each filled on the
+// launch's stream right before its kernel (so a captured graph refills its slot at every replay).
+// A slot comes round again after kTableSlots launches; the in-process harness (tests, tools) keeps
+// far fewer in flight.  The ring is allocated at a device's first launch, which therefore must not
+// happen under stream capture.
+constexpr int kTableSlots = 64, kTableDevices = 64;
+static A2ASeg* nextTableSlot() {
+  static std::mutex mu;
+  static A2ASeg* ring[kTableDevices] = {};
+  static unsigned next[kTableDevices] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kTableDevices) return nullptr;
+  std::lock_guard<std::mutex> lk(mu);
+  if (!ring[dev] && hipMalloc((void**)&ring[dev], (size_t)kTableSlots * sizeof(A2ATableArg)) != hipSuccess) {
+    ring[dev] = nullptr;
+    return nullptr;
+  }
+  return ring[dev] + (size_t)(next[dev]++ % kTableSlots) * kMaxRanks * kMaxRanks;
+}
+
+// segs: host, [nviews][nranks].
+int launchAllToAll(const mscclppAmdRankView* views, int nviews, int nranks, const A2ASeg* segs, int nblocks,
+                   int nthreads, uint64_t budget, hipStream_t s) {
+  if (nblocks <= 0) {
+    uint64_t most = 0;
+    for (int i = 0; i < nviews; ++i) {
+      uint64_t sum = 0;
+      for (int p = 0; p < nranks; ++p) sum += segs[i * nranks + p].len;
+      most = sum > most ? sum : most;
+    }
+    nblocks = alltoallDefaultBlocks(most);
+  }
+  if (nthreads <= 0) nthreads = 512;
+  if (nblocks > kMaxChannels || nthreads > 512 || nthreads % 64 || nthreads < 64) return 4;
+  for (int i = 0; i < nviews * nranks; ++i)
+    if (((segs[i].len + nblocks - 1) / nblocks + 15) / 16 * 16 > kBlkOffsetLimit) return 5;
+  if (nviews == 1) {
+    A2AArgs<1> a{};
+    a.views.v[0] = views[0];
+    for (int p = 0; p < nranks; ++p) a.segs.s[p] = segs[p];
+    a.budget = budget;
+    a.trace = g_mscclppAmdTrace;
+    a.nranks = nranks;
+    if (!grid_coresident(alltoallKernel<1, 4>, nthreads, nblocks)) return 5;
+    hipLaunchKernelGGL((alltoallKernel<1, 4>), dim3(nblocks), dim3(nthreads), 0, s, a);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+  }
+  if (!grid_coresident(alltoallKernel<kMaxRanks, 4>, nthreads, (long)nblocks * nviews)) return 5;
+  A2ATableArg t{};
+  for (int i = 0; i < nviews; ++i)
+    for (int p = 0; p < nranks; ++p) t.s[i * kMaxRanks + p] = segs[i * nranks + p];
+  A2ASeg* slot = nextTableSlot();
+  if (!slot) return 1;
+  hipLaunchKernelGGL(alltoallTableKernel, dim3(1), dim3(64), 0, s, t, slot);
+  A2AArgs<kMaxRanks> a{};
+  for (int i = 0; i < nviews; ++i) a.views.v[i] = views[i];
+  a.segs.tab = slot;
+  a.budget = budget;
+  a.trace = g_mscclppAmdTrace;
+  a.nranks = nranks;
+  hipLaunchKernelGGL((alltoallKernel<kMaxRanks, 4>), dim3(nblocks, nviews), dim3(nthreads), 0, s, a);
+  return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+}  // namespace mscclpp_amd
