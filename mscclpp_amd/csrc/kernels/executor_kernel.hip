@@ -304,6 +304,10 @@ __device__ void handleReadReduceSend(const Op& op, const Ctx& c, uint64_t offset
 }
 
 // handleReduceSend (:446-507): out = src (+) local inputs in listed order; optionally to remotes.
+// Departure: the reuse-scratch wrap of local input k+1 is keyed on that input's own buffer type.
+// The reference keys it on outputBufferRefs[k+1] (:466-468), a slot that `re` never fills and that
+// holds a remote buffer index for `res`, so a pipelined reduction over wrapped scratch windows
+// would read bytes nobody wrote.
 template <int DT, bool ReuseScratch, bool SendToRemote>
 __device__ void handleReduceSend(const Op& op, const Ctx& c, uint64_t offset, uint64_t unitSize) {
   if (op.inSize[0] <= offset) return;
@@ -314,7 +318,7 @@ __device__ void handleReduceSend(const Op& op, const Ctx& c, uint64_t offset, ui
   const uint8_t* lin[kMaxBuffersPerOp];
   uint8_t* rout[kMaxBuffersPerOp];
   for (uint32_t k = 0; k < nIn; ++k)
-    lin[k] = getBuffer(c, op.inRef[k + 1]) + op.inOff[k + 1] + getOffset<ReuseScratch>(c, op.outRef[k + 1], offset);
+    lin[k] = getBuffer(c, op.inRef[k + 1]) + op.inOff[k + 1] + getOffset<ReuseScratch>(c, op.inRef[k + 1], offset);
   for (uint32_t k = 0; k < nOut; ++k) {
     const uint8_t r = op.outRef[k + 1];
     rout[k] = (uint8_t*)c.h->remotePtr[r] + op.outOff[k + 1] + getOffset<ReuseScratch>(c, c.h->remoteType[r], offset);

@@ -430,9 +430,11 @@ class ExecutorOracle:
                     arr = self._remote(ranks, r, tb, ref)
                     t = rk.plan.remote[tb["remote"][ref]][1]
                     o0 = off + reuse_off(t, offset)
-                else:  # handleReduceSend reads local buffers (offset rule keyed on the output ref, :468)
+                else:  # handleReduceSend reads local buffers; the wrap is keyed on the input's own type
+                    # (the reference keys it on output slot k+1, :468, which `re` never fills and
+                    # which is a remote buffer index for `res`: a documented departure)
                     arr = self._local(rk, ref, soff)
-                    o0 = off + reuse_off(outs[k + 1][0] if k + 1 < len(outs) else ref, offset)
+                    o0 = off + reuse_off(ref, offset)
                 acc = reduce_words(dt, red, acc, arr[o0:o0 + n].view(np.uint32))
             dst = self._local(rk, outs[0][0], soff)
             d0 = outs[0][1] + reuse_off(outs[0][0], offset)

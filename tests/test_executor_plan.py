@@ -13,6 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLANS = os.path.join(ROOT, "tests", "golden", "plans")
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import executor_oracle as E  # noqa: E402
+import executor_cases as X  # noqa: E402
 
 GENERATED = sorted(f for f in os.listdir(PLANS) if f.endswith(".json"))
 REF_PLANS = "/root/reference/test/execution-files"
@@ -27,9 +28,11 @@ def _nranks(doc):
 
 
 def _sizes(doc):
+    """Bytes of the chunked (larger) buffer; a reuse-scratch plan also gets a chunk above the wrap
+    threshold, where scratch chunks are laid out by window and not by message chunk."""
     g = doc["gpus"][0]
     c = max(g["input_chunks"], g["output_chunks"]) * doc.get("buffer_alignment", 16)
-    return [c, c * 4, c * 1024, c * 1000 + c * 7]
+    return [c, c * 4, c * 1024, c * 1000 + c * 7] + ([c * 2561] if doc.get("reuse_resources") else [])
 
 
 def _check_plan(built, path):
@@ -42,8 +45,9 @@ def _check_plan(built, path):
         assert plan.name() == doc["name"] and plan.collective() == doc["collective"]
         assert plan.is_in_place() == doc["inplace"]
         for size in _sizes(doc):
-            got = plan.describe(size, size)
-            exp = E.RankPlan(doc, rank, size, size).describe()
+            ib, ob = X.in_out_bytes(doc, size)
+            got = plan.describe(ib, ob)
+            exp = E.RankPlan(doc, rank, ib, ob).describe()
             assert got == json.loads(json.dumps(exp)), (path, rank, size)
 
 
@@ -72,22 +76,103 @@ def test_oracle_known_answer_reference_plans(fname, dtype):
 @pytest.mark.parametrize("fname", GENERATED)
 @pytest.mark.parametrize("dtype", ["i32", "u32"])
 def test_oracle_known_answer(fname, dtype):
-    """Integer sums are exact whatever the order: every rank must end with the plain sum."""
+    """Integer results are exact whatever the order: every rank must end with the plain numpy answer
+    of the plan's collective and reduce operation (sum, min, concatenation).  `min` through the
+    packet reductions starts from zero words, so with these non-negative inputs it must give zeros."""
     with open(os.path.join(PLANS, fname)) as f:
         doc = json.load(f)
     n = _nranks(doc)
     eo = E.ExecutorOracle(doc, n)
-    nbytes = _sizes(doc)[1] * 8
+    ib, ob = X.in_out_bytes(doc, _sizes(doc)[1] * 8)
     rng = np.random.default_rng(5)
     npdt = np.int32 if dtype == "i32" else np.uint32
     for _ in range(3):
-        ins = [rng.integers(0, 1 << 20, nbytes // 4).astype(npdt).view(np.uint8).copy() for _ in range(n)]
-        exp = sum(a.view(npdt).astype(np.int64) for a in ins).astype(npdt)
-        outs = ins if doc["inplace"] else [np.zeros_like(a) for a in ins]
-        res = eo.execute(ins, outs, dtype)
+        ins = [rng.integers(0, 1 << 20, ib // 4).astype(npdt).view(np.uint8).copy() for _ in range(n)]
+        exp = X.numpy_answer(doc, dtype, ins)
+        if exp is None:
+            assert X.is_min(doc) and X.all_ops(doc) & X.PACKET_REDUCES and doc["collective"] == "allreduce"
+            exp = [np.zeros(ob, np.uint8)] * n
+        src = [a.copy() for a in ins]
+        outs = src if doc["inplace"] else [np.full(ob, 0xA5, np.uint8) for _ in range(n)]
+        res = eo.execute(src, outs, dtype)
         for r in range(n):
-            got = res[r][0 if doc["inplace"] else 1].view(npdt)
-            assert np.array_equal(got, exp)
+            assert np.array_equal(res[r][0 if doc["inplace"] else 1], exp[r]), r
+            assert doc["inplace"] or np.array_equal(res[r][0], ins[r]), r
+
+
+# ---- the tables of tests/test_executor_ops_gpu.py, on the CPU -------------------------------------
+
+# every case of executeOp (executor_kernel.hip) but the multimem ones, by plan operation name
+DEVICE_OPS = {"nop", "barrier", "signal", "wait", "rlxsignal", "rlxwait", "put", "pws", "pwsf", "get", "copy", "rres",
+              "rre", "res", "re", "ppkt", "rppkt", "respkt", "repkt", "recspkt", "recpkt", "upkt", "cpkt",
+              "sem_acquire", "sem_release", "pipeline", "flush"}
+# executionKernel<DT, LL16, ReuseScratch> x the reduce operation an operation carries
+KERNEL_VARIANTS = {(reuse, pkt, op) for reuse in (False, True) for pkt in ("LL16", "LL8") for op in ("sum", "min")}
+
+
+def test_gpu_fixtures_cover_the_device_switch():
+    """A handler added to the device switch (and to the oracle's OPS) without a fixture that a GPU
+    test executes fails here, as does a kernel variant no GPU case launches."""
+    ops = set()
+    for f in X.gpu_plans():
+        with open(os.path.join(PLANS, f)) as fh:
+            ops |= X.all_ops(json.load(fh))
+    assert ops == DEVICE_OPS
+    assert DEVICE_OPS == E.OPS
+    assert X.kernel_variants() == KERNEL_VARIANTS
+    # the tables run every generated fixture somewhere
+    assert set(GENERATED) <= set(X.gpu_plans())
+
+
+def test_gpu_case_tables_are_well_formed():
+    for n, cases in X.CASES.items():
+        ids = [c.id for c in cases]
+        assert len(set(ids)) == len(ids)
+        for c in cases:
+            assert c.nranks() == n and all(len(X.doc(f)["gpus"]) == n for f, _ in c.steps)
+            for f, msg in c.steps:
+                d = X.doc(f)
+                assert max(X.in_out_bytes(d, msg)) <= X.ARENA_BYTES - 2 * X.GUARD_BYTES
+                if d["protocol"] == "LL":  # a slice must be whole packets
+                    assert d["buffer_alignment"] % (8 if c.pkt == "LL16" else 4) == 0, c.id
+    # the reuse plans run below, at and above the wrap threshold
+    assert min(X.REUSE_CHUNKS) < X.REUSE_THRESHOLD < max(X.REUSE_CHUNKS) and X.REUSE_THRESHOLD in X.REUSE_CHUNKS
+    assert E.RankPlan(X.doc("allreduce_reuse_n2.json"), 0, 1 << 16, 1 << 16).max_scratch_chunk(E.PREDEFINED_SCRATCH) == \
+        X.REUSE_THRESHOLD
+
+
+def _int_cases():
+    seen, out = set(), []
+    for n, cases in X.CASES.items():
+        for c in cases:
+            key = (tuple(c.steps), c.dtype, c.pkt)
+            if c.dtype in X.NP_INT and key not in seen:
+                seen.add(key)
+                out.append(c)
+    return out
+
+
+@pytest.mark.parametrize("case", _int_cases(), ids=lambda c: c.id)
+def test_oracle_known_answer_at_gpu_sizes(case):
+    """Every i32 / u32 GPU case on the CPU: the oracle does not deadlock and equals the numpy answer
+    (inputs with negative and >= 2^31 values; min through packets has no such answer)."""
+    for k, (ins, outs, plain) in enumerate(X.run_oracle(case, 1)):
+        d = X.doc(case.steps[k][0])
+        if plain is None:
+            assert X.is_min(d) and X.all_ops(d) & X.PACKET_REDUCES
+            continue
+        for r in range(case.nranks()):
+            assert np.array_equal(outs[r], plain[r]), (case.id, k, r)
+
+
+def test_get_addresses_local_by_source_and_remote_by_destination():
+    """handleGet as the reference has it (execution_kernel.hpp:129-142): `get src=[peer input, index 1]
+    dst=[output, index 0]` lands the peer's chunk 0 in my chunk 1."""
+    d = X.doc("get_offsets_n2.json")
+    ins = [np.arange(64, dtype=np.uint8) + 100 * r for r in range(2)]
+    res = E.ExecutorOracle(d, 2).execute([a.copy() for a in ins], [np.zeros(64, np.uint8) for _ in range(2)], "u32")
+    for r in range(2):
+        assert np.array_equal(res[r][1], np.concatenate([ins[r][32:], ins[1 - r][:32]]))
 
 
 def test_oracle_flag_and_double_scratch():
