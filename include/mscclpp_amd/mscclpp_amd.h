@@ -195,6 +195,17 @@ typedef struct {
  * 4 GiB (more workgroups carry it), or the grid cannot be resident at once. */
 int mscclppAmdAllToAllLaunch(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdAllToAllSeg* segs,
                              int nblocks, int nthreads, uint64_t budgetTicks, void* stream);
+/* Reduce to `root` by a zero-copy pull-reduce at the root (kernels/reduce.hip): the root reads
+ * `bytes` of every rank's input (views[root].peerInput[q] = rank q's send buffer), reduces in ring
+ * order root, root + 1, ..., root + n - 1 (mod n) with the arithmetic of the AllReduce kernels, and
+ * stores the result into its own output; the other ranks only hand-shake (their output is not
+ * touched and may be NULL).  In place on the root (input == output) is carried.  dtype: any reduce
+ * type code above; bytes: a multiple of its element size; pointers need the element's alignment only.
+ * nblocks <= 0: 32 KiB per workgroup, 8..64; every rank of one collective must launch the same
+ * nblocks.  4: a null or out-of-range argument or launch shape (nothing is launched); 5: a
+ * workgroup's range exceeds 4 GiB (more workgroups carry it), or the grid cannot be resident at once. */
+int mscclppAmdReduceLaunch(const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes, int dtype, int op,
+                           int root, int nblocks, int nthreads, uint64_t budgetTicks, void* stream);
 /* Scratch bytes per rank (both halves) that `algo` needs for `bytes` (0 if unsupported).  For the
  * pipelined RS+AG this is one stage at the default shape (32 x 512); a larger shape needs
  * mscclppAmdScratchRequiredShape. */
@@ -225,7 +236,8 @@ int mscclppAmdTunedConfigSource(const char* collective, int nranks, size_t bytes
 // 3 reduce + all-gather stores issued, 4 end; zero-copy: 0 start, 1 entry handshake done, 2 reduce +
 // all-gather stores issued, 3 end; LL16: 0 start, 1 step 1 (puts), 2 step 2 (reduce + broadcast),
 // 3 step 3 (unpack) done; LL8: 0 start, 1 puts issued, 2 end; AllToAll: 0 start, 1 entry handshake
-// done, 2 segments stored, 3 end.  buf = NULL turns it off.  Returns 0,
+// done, 2 segments stored, 3 end; Reduce: 0 start, 1 entry handshake done, 2 result stored (root),
+// 3 end.  buf = NULL turns it off.  Returns 0,
 // or 4 when the buffer is too small.
 #define MSCCLPP_AMD_TRACE_BYTES ((size_t)MSCCLPP_AMD_MAX_RANKS * 256 * 8 * 8)
 int mscclppAmdTraceSet(void* buf, size_t bytes);

@@ -143,6 +143,8 @@ def lib():
         "ncclCommSplit": [vp, i32, i32, ctypes.POINTER(vp), vp],
         "mscclppAmdBroadcastLaunch": [ctypes.POINTER(RankView), i32, i32, sz, i32, i32, i32, u64, vp],
         "mscclppAmdAllToAllLaunch": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(AllToAllSeg), i32, i32, u64, vp],
+        "mscclppAmdReduceLaunch": [ctypes.POINTER(RankView), i32, i32, sz, i32, i32, i32, i32, i32, u64, vp],
+        "ncclReduce": [vp, vp, sz, i32, i32, i32, vp, vp],
         "ncclAllToAll": [vp, vp, sz, i32, vp, vp],
         "ncclAllToAllv": [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp, ctypes.POINTER(sz), ctypes.POINTER(sz), i32, vp,
                           vp],
@@ -325,6 +327,7 @@ TRACE_PHASES = {
     "packet": ("step1_put", "step2_reduce_bcast", "step3_unpack"),
     "allpair": ("put", "reduce"),
     "alltoall": ("entry_handshake", "pull", "exit_handshake"),
+    "reduce": ("entry_handshake", "pull_reduce", "exit_handshake"),
 }
 
 
@@ -472,6 +475,22 @@ class InProcessRanks:
         code = lib().mscclppAmdAllToAllLaunch(arr, n, n, tab, nblocks, nthreads, budget_ticks, stream_ptr(stream))
         check(code, "in-process all_to_all")
 
+    def reduce(self, inputs, outputs, root, op=SUM, nblocks=0, nthreads=0, budget_ticks=500_000_000, stream=None,
+               accum=None):
+        """ncclReduce for in-process ranks: outputs[root] <- inputs[root] (op) inputs[root + 1] (op) ...
+        in ring order from the root.  outputs[r] is not touched for r != root and may be None."""
+        dt = reduce_code(inputs[0].dtype, accum)
+        nbytes = inputs[0].numel() * inputs[0].element_size()
+        arr = self.views(inputs, [inputs[r] if o is None else o for r, o in enumerate(outputs)])
+        for r, o in enumerate(outputs):
+            if o is None:
+                arr[r].output = None
+                for q in range(self.n):
+                    arr[q].peerOutput[r] = None
+        code = lib().mscclppAmdReduceLaunch(arr, self.n, self.n, nbytes, dt, op, root, nblocks, nthreads, budget_ticks,
+                                            stream_ptr(stream))
+        check(code, "in-process reduce")
+
     def errors(self):
         return [int(e[0].item()) for e in self.err]
 
@@ -560,6 +579,16 @@ class Communicator:
         recv = send if recv is None else recv
         check(lib().ncclBroadcast(ctypes.c_void_p(send.data_ptr()), ctypes.c_void_p(recv.data_ptr()), recv.numel(),
                                   NCCL_DTYPES[recv.dtype], root, self.comm, stream_ptr(stream)), "ncclBroadcast")
+        return recv
+
+    def reduce(self, send, recv=None, root=0, op="sum", stream=None):
+        """ncclReduce(send, recv, count, dtype, op, root, comm, stream): recv is written on the root only
+        (None: in place on the root, no receive buffer elsewhere)."""
+        if recv is None and self.rank == root:
+            recv = send
+        check(lib().ncclReduce(ctypes.c_void_p(send.data_ptr()), ctypes.c_void_p(None if recv is None else recv.data_ptr()),
+                               send.numel(), nccl_dtype(send.dtype), NCCL_OPS[op], root, self.comm, stream_ptr(stream)),
+              "ncclReduce")
         return recv
 
     def all_to_all(self, send, recv, stream=None):

@@ -35,6 +35,9 @@ int launchBroadcast(const mscclppAmdRankView* views, int nviews, int nranks, siz
 int launchAllToAll(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdAllToAllSeg* segs,
                    int nblocks, int nthreads, uint64_t budget, hipStream_t s);
 int alltoallDefaultBlocks(uint64_t maxRecvBytes);
+int launchReduce(const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes, int dtype, int op, int root,
+                 int nblocks, int nthreads, uint64_t budget, hipStream_t s);
+int reduceDefaultBlocks(uint64_t bytes);
 size_t ll16ScratchRequired(int nranks, size_t bytes, int dtype);
 size_t ll8ScratchRequired(int nranks, size_t bytes, int dtype);
 size_t testLLScratchRequired(int nranks, size_t bytes);
@@ -703,6 +706,22 @@ struct ncclComm {
     return rc;
   }
 
+  // Reduce to `root` by a zero-copy pull-reduce at the root (kernels/reduce.hip).  The send buffer is
+  // what the root reads, so it is the one registered, on every rank (collective on first use, cached
+  // per allocation, pinned under capture: the matching-buffer contract of AllToAll); the result is
+  // stored by the root into its own receive buffer, which is never registered.  recv is used on the
+  // root only.  Every rank derives the same grid from the byte count.
+  int reduce(const void* send, void* recv, size_t bytes, int dtype, int op, int root, hipStream_t stream) {
+    std::lock_guard<std::mutex> lk(mu);
+    touched.clear();
+    mscclppAmdRankView v = baseView(send, rank == root ? recv : nullptr);
+    const auto ins = registerOutput(const_cast<void*>(send), stream);
+    for (int r = 0; r < nranks; ++r) v.peerInput[r] = ins[r];
+    const int rc = launchReduce(&v, 1, nranks, bytes, dtype, op, root, 0, 0, spinBudgetTicks(), stream);
+    recordUses(stream);
+    return rc;
+  }
+
   // AllToAllv's send buffers.  Its ranks pass buffers of different sizes, which each rank's
   // allocator places on its own, so "my buffer X goes with your buffer Y" -- what userRegs caches,
   // keyed by the local buffer alone -- does not hold from one call to the next.  The call's own
@@ -1011,7 +1030,8 @@ struct VendorNccl {
 // The vendor library named by MSCCLPP_AMD_NCCL_LIB_PATH (or MSCCLPP_NCCL_LIB_PATH), or null.
 const VendorNccl* vendorNccl();
 // MSCCLPP_AMD_FORCE_NCCL_FALLBACK_OPERATION ("all" or a comma list of allreduce, allgather,
-// reducescatter, broadcast, alltoall, alltoallv) names `op`.
+// reducescatter, broadcast, alltoall, alltoallv, reduce) names `op`: a whole list entry equals it, so
+// "reducescatter" does not name "reduce".
 bool forcedFallback(const char* op);
 // ncclCommInitRank with the bootstrap's connect / receive timeout given (ncclCommInitRank takes it
 // from MSCCLPP_AMD_BOOTSTRAP_TIMEOUT_S); commId is the 128-byte unique id.  Returns an ncclResult_t.

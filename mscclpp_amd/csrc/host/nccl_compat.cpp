@@ -3,16 +3,18 @@
 //
 //  * native here: ncclBroadcast / ncclBcast (zero-copy pull from the root), ncclAllToAll /
 //    ncclAllToAllv (zero-copy pull from every peer, kernels/alltoall.hip; the reference leaves both
-//    to the vendor library, nccl.cc:794-821), ncclCommSplit (nccl.cc:405-435),
+//    to the vendor library, nccl.cc:794-821), ncclReduce (zero-copy pull-reduce at the root,
+//    kernels/reduce.hip, for the data types and operations AllReduce carries; the reference returns
+//    ncclInternalError without a vendor library, nccl.cc:521-542), ncclCommSplit (nccl.cc:405-435),
 //    ncclCommInitRankScalable with one id, ncclCommRegister / Deregister and ncclCommWindowRegister /
 //    Deregister (the path registers buffers lazily on first use, so these only hand the pointer back);
 //  * forwarded to the vendor library when MSCCLPP_AMD_NCCL_LIB_PATH (or the reference's
 //    MSCCLPP_NCCL_LIB_PATH) names it -- the reference's dlopen fallback, nccl.cc:72-160, :323-346:
-//    ncclReduce, ncclSend/Recv, ncclRedOpCreatePreMulSum/Destroy, ncclGroupSimulateEnd, group calls,
-//    and AllReduce / AllGather / ReduceScatter / Broadcast / AllToAll(v) for data types and
+//    ncclSend/Recv, ncclRedOpCreatePreMulSum/Destroy, ncclGroupSimulateEnd, group calls,
+//    and AllReduce / AllGather / ReduceScatter / Broadcast / AllToAll(v) / Reduce for data types and
 //    operations this path does not carry or that MSCCLPP_AMD_FORCE_NCCL_FALLBACK_OPERATION
-//    (reference: MSCCLPP_FORCE_NCCL_FALLBACK_OPERATION, "all" or a comma list; keys alltoall and
-//    alltoallv for the two above) forces there.  Without a vendor library the operations not
+//    (reference: MSCCLPP_FORCE_NCCL_FALLBACK_OPERATION, "all" or a comma list; keys alltoall,
+//    alltoallv and reduce for the three above) forces there.  Without a vendor library the operations not
 //    carried here return ncclInternalError, as the reference does for the same cases.
 #include <dlfcn.h>
 #include <sys/stat.h>
@@ -225,9 +227,22 @@ ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, nccl
         HIPCHECK(hipMemcpyAsync(recvbuff, sendbuff, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
       return (int)ncclSuccess;
     }
-    if (vendorComm(comm) && vendorNccl()->Reduce)
+    const bool isRoot = root == comm->rank;
+    if (root < 0 || root >= comm->nranks) return (int)ncclInvalidArgument;
+    if (!sendbuff || count == 0 || (isRoot && !recvbuff)) return (int)ncclInvalidArgument;
+    const size_t bytes = count * ncclTypeBytes(datatype);
+    // in place on the root is send == recv; any other overlap would have the root store into
+    // bytes of its send buffer that another lane still reads
+    if (isRoot && bytes && sendbuff != recvbuff && rangesOverlap(sendbuff, bytes, recvbuff, bytes)) {
+      warn("ncclReduce: the root's send and receive ranges overlap without being identical");
+      return (int)ncclInvalidArgument;
+    }
+    const int dt = dtypeFromNccl(datatype), o = opFromNccl(op);
+    if (vendorComm(comm) && vendorNccl()->Reduce && (dt < 0 || o < 0 || forcedFallback("reduce")))
       return (int)vendorNccl()->Reduce(sendbuff, recvbuff, count, datatype, op, root, vendorComm(comm), stream);
-    return (int)unavailable("ncclReduce");
+    if (dt < 0 || o < 0) return (int)unavailable("ncclReduce of this data type or operation");
+    // a non-root rank's recvbuff is ignored (and may be null)
+    return comm->reduce(sendbuff, isRoot ? recvbuff : nullptr, bytes, dt, o, root, (hipStream_t)stream);
   });
 }
 
@@ -468,6 +483,34 @@ int mscclppAmdAllToAllLaunch(const mscclppAmdRankView* views, int nviews, int nr
     }
     return mscclpp_amd::launchAllToAll(views, nviews, nranks, segs, nblocks, nthreads,
                                        budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream);
+  });
+}
+
+// Reduce for in-process ranks: views as above, peerInput[q] = rank q's send buffer (read by the root
+// only), output = the receive buffer (used on the root only).  Everything is checked before a
+// device is touched; a refusal launches nothing.
+int mscclppAmdReduceLaunch(const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes, int dtype, int op,
+                           int root, int nblocks, int nthreads, uint64_t budgetTicks, void* stream) {
+  return guarded([&] {
+    if (!views || nviews < 1 || nranks < 2 || nranks > MSCCLPP_AMD_MAX_RANKS) return (int)ncclInvalidArgument;
+    if (nviews != 1 && nviews != nranks) return (int)ncclInvalidArgument;
+    if (root < 0 || root >= nranks) return (int)ncclInvalidArgument;
+    if (dtype < 0 || dtype >= MSCCLPP_AMD_NUM_DTYPES || (op != MSCCLPP_AMD_SUM && op != MSCCLPP_AMD_MIN))
+      return (int)ncclInvalidArgument;
+    if (bytes == 0) return (int)ncclInvalidArgument;  // (a byte count that splits an element: launchReduce)
+    for (int i = 0; i < nviews; ++i) {
+      const mscclppAmdRankView& v = views[i];
+      if (!v.input || !v.tokens || !v.expected || !v.err) return (int)ncclInvalidArgument;
+      if (v.rank < 0 || v.rank >= nranks) return (int)ncclInvalidArgument;
+      for (int q = 0; q < nranks; ++q)
+        if (!v.peerTokens[q]) return (int)ncclInvalidArgument;
+      if (v.rank != root) continue;
+      if (!v.output) return (int)ncclInvalidArgument;
+      for (int q = 0; q < nranks; ++q)
+        if (!v.peerInput[q]) return (int)ncclInvalidArgument;
+    }
+    return mscclpp_amd::launchReduce(views, nviews, nranks, bytes, dtype, op, root, nblocks, nthreads,
+                                     budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream);
   });
 }
 

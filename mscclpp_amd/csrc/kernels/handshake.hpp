@@ -1,4 +1,4 @@
-// The per-workgroup token handshake of the bulk collectives (allreduce_bulk.hip, alltoall.hip).
+// The per-workgroup token handshake of the bulk collectives (allreduce_bulk.hip, alltoall.hip, reduce.hip).
 #pragma once
 
 #include "common.hpp"
