@@ -206,6 +206,31 @@ int mscclppAmdAllToAllLaunch(const mscclppAmdRankView* views, int nviews, int nr
  * workgroup's range exceeds 4 GiB (more workgroups carry it), or the grid cannot be resident at once. */
 int mscclppAmdReduceLaunch(const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes, int dtype, int op,
                            int root, int nblocks, int nthreads, uint64_t budgetTicks, void* stream);
+/* Send / Recv by a zero-copy pull (kernels/sendrecv.hip): one launch runs a table of point-to-point
+ * operations, in table order.  An operation moves `bytes` from `send` on rank `src` to `recv` on
+ * rank `dst`: the receiver reads `send` -- the address at which the view of rank `dst` has the
+ * sender's buffer mapped; a plain device pointer for in-process ranks -- and stores into `recv`;
+ * the sender's view only signals and waits, and reads neither pointer.  A view runs the operations
+ * in which it is src or dst (only tokens, peerTokens, expected, err and rank of a view are used).
+ * Buffers may start at any byte (16-byte aligned starts on both sides take the fast path).
+ * nblocks <= 0: each operation's workgroups from its byte count (mscclppAmdSendRecvDefaultBlocks:
+ * 128 KiB each, 1..64); nblocks > 0: that many for every operation (<= 128) -- the same on both
+ * sides of every operation.  Sender and receiver of a pair must list the operations between them in
+ * the same order.
+ * 4: a null pointer, nviews not 1 or nranks, src == dst, a rank out of range, nops of 0 or above
+ * MSCCLPP_AMD_SENDRECV_MAX_OPS, bytes of 0, nblocks > 128, or nthreads not a multiple of 64 in
+ * 64..512 (all checked before any device call; nothing is launched); 5: a workgroup's sub-range
+ * exceeds 4 GiB (more workgroups carry it), or the grid cannot be resident at once. */
+#define MSCCLPP_AMD_SENDRECV_MAX_OPS 64
+typedef struct {
+  int32_t src, dst;
+  const void* send;
+  void* recv;
+  uint64_t bytes;
+} mscclppAmdSendRecvOp;
+int mscclppAmdSendRecvLaunch(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdSendRecvOp* ops,
+                             int nops, int nblocks, int nthreads, uint64_t budgetTicks, void* stream);
+int mscclppAmdSendRecvDefaultBlocks(uint64_t bytes);
 /* Scratch bytes per rank (both halves) that `algo` needs for `bytes` (0 if unsupported).  For the
  * pipelined RS+AG this is one stage at the default shape (32 x 512); a larger shape needs
  * mscclppAmdScratchRequiredShape. */
@@ -237,7 +262,8 @@ int mscclppAmdTunedConfigSource(const char* collective, int nranks, size_t bytes
 // all-gather stores issued, 3 end; LL16: 0 start, 1 step 1 (puts), 2 step 2 (reduce + broadcast),
 // 3 step 3 (unpack) done; LL8: 0 start, 1 puts issued, 2 end; AllToAll: 0 start, 1 entry handshake
 // done, 2 segments stored, 3 end; Reduce: 0 start, 1 entry handshake done, 2 result stored (root),
-// 3 end.  buf = NULL turns it off.  Returns 0,
+// 3 end; Send/Recv: 0 start, 1 readies posted, 2 receives stored, 3 dones seen.  buf = NULL turns it
+// off.  Returns 0,
 // or 4 when the buffer is too small.
 #define MSCCLPP_AMD_TRACE_BYTES ((size_t)MSCCLPP_AMD_MAX_RANKS * 256 * 8 * 8)
 int mscclppAmdTraceSet(void* buf, size_t bytes);

@@ -8,6 +8,7 @@ the same argument meaning and error behaviour).  PyTorch is used only for device
 streams.  There is no fallback: if the library is missing, importing a GPU entry point raises.
 """
 import collections
+import contextlib
 import ctypes
 import os
 
@@ -94,6 +95,15 @@ class AllToAllSeg(ctypes.Structure):
     _fields_ = [("srcOff", ctypes.c_uint64), ("dstOff", ctypes.c_uint64), ("len", ctypes.c_uint64)]
 
 
+class SendRecvOp(ctypes.Structure):
+    """mscclppAmdSendRecvOp: `bytes` move from `send` on rank `src` to `recv` on rank `dst` (the receiver pulls)."""
+    _fields_ = [("src", ctypes.c_int32), ("dst", ctypes.c_int32), ("send", ctypes.c_void_p), ("recv", ctypes.c_void_p),
+                ("bytes", ctypes.c_uint64)]
+
+
+SENDRECV_MAX_OPS = 64
+
+
 class UniqueId(ctypes.Structure):
     _fields_ = [("internal", ctypes.c_char * 128)]
 
@@ -145,6 +155,12 @@ def lib():
         "mscclppAmdAllToAllLaunch": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(AllToAllSeg), i32, i32, u64, vp],
         "mscclppAmdReduceLaunch": [ctypes.POINTER(RankView), i32, i32, sz, i32, i32, i32, i32, i32, u64, vp],
         "ncclReduce": [vp, vp, sz, i32, i32, i32, vp, vp],
+        "mscclppAmdSendRecvLaunch": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(SendRecvOp), i32, i32, i32, u64, vp],
+        "mscclppAmdSendRecvDefaultBlocks": [u64],
+        "ncclSend": [vp, sz, i32, i32, vp, vp],
+        "ncclRecv": [vp, sz, i32, i32, vp, vp],
+        "ncclGroupStart": [],
+        "ncclGroupEnd": [],
         "ncclAllToAll": [vp, vp, sz, i32, vp, vp],
         "ncclAllToAllv": [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), vp, ctypes.POINTER(sz), ctypes.POINTER(sz), i32, vp,
                           vp],
@@ -328,6 +344,7 @@ TRACE_PHASES = {
     "allpair": ("put", "reduce"),
     "alltoall": ("entry_handshake", "pull", "exit_handshake"),
     "reduce": ("entry_handshake", "pull_reduce", "exit_handshake"),
+    "sendrecv": ("post_ready", "pull", "wait_done"),
 }
 
 
@@ -491,6 +508,29 @@ class InProcessRanks:
                                             stream_ptr(stream))
         check(code, "in-process reduce")
 
+    def send_recv(self, ops, nblocks=0, nthreads=0, budget_ticks=500_000_000, stream=None):
+        """ncclSend / ncclRecv (a whole group) for in-process ranks, one launch.  ops: (src, dst, send,
+        recv) in table order -- `send` on rank src (a tensor, read in place by rank dst) lands in
+        `recv` on rank dst; both are flat tensors of equal byte size and may be views at any byte
+        offset.  nblocks > 0: that many workgroups for every operation."""
+        tab = (SendRecvOp * len(ops))()
+        for i, (src, dst, send, recv) in enumerate(ops):
+            nbytes = send.numel() * send.element_size()
+            assert nbytes == recv.numel() * recv.element_size()
+            tab[i] = SendRecvOp(src, dst, send.data_ptr(), recv.data_ptr(), nbytes)
+        arr = (RankView * self.n)()
+        for r in range(self.n):
+            v = arr[r]
+            for q in range(self.n):
+                v.peerTokens[q] = self.tokens[q].ptr
+            v.tokens = self.tokens[r].ptr
+            v.expected = self.expected[r].data_ptr()
+            v.err = self.err[r].data_ptr()
+            v.rank = r
+        code = lib().mscclppAmdSendRecvLaunch(arr, self.n, self.n, tab, len(ops), nblocks, nthreads, budget_ticks,
+                                              stream_ptr(stream))
+        check(code, "in-process send_recv")
+
     def errors(self):
         return [int(e[0].item()) for e in self.err]
 
@@ -606,6 +646,31 @@ class Communicator:
                                   ctypes.c_void_p(recv.data_ptr()), arr(recv_counts), arr(recv_displs),
                                   nccl_dtype(send.dtype), self.comm, stream_ptr(stream)), "ncclAllToAllv")
         return recv
+
+    def send(self, t, peer, stream=None):
+        """ncclSend(t, count, dtype, peer, comm, stream): rank `peer` pulls t's bytes with its matching
+        recv.  Any dtype is carried (a byte move).  Inside `with comm.group():` the call is queued."""
+        check(lib().ncclSend(ctypes.c_void_p(t.data_ptr()), t.numel(), nccl_dtype(t.dtype), peer, self.comm,
+                             stream_ptr(stream)), "ncclSend")
+
+    def recv(self, t, peer, stream=None):
+        """ncclRecv(t, count, dtype, peer, comm, stream): t receives what rank `peer` sends."""
+        check(lib().ncclRecv(ctypes.c_void_p(t.data_ptr()), t.numel(), nccl_dtype(t.dtype), peer, self.comm,
+                             stream_ptr(stream)), "ncclRecv")
+        return t
+
+    @staticmethod
+    @contextlib.contextmanager
+    def group():
+        """ncclGroupStart / ncclGroupEnd around the block: the sends and receives issued inside run
+        in one kernel per (communicator, stream) at the outermost end, which raises their errors."""
+        check(lib().ncclGroupStart(), "ncclGroupStart")
+        try:
+            yield
+        except BaseException:
+            lib().ncclGroupEnd()  # the depth goes back down; the body's error is the one reported
+            raise
+        check(lib().ncclGroupEnd(), "ncclGroupEnd")
 
     def register_buffer(self, t):
         """Collective: every rank's matching buffer as mapped here (list of nranks device pointers)."""

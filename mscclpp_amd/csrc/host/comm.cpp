@@ -518,10 +518,12 @@ ncclResult_t ncclAllGather(const void* sendbuff, void* recvbuff, size_t sendcoun
   });
 }
 
-// Native operations run when called (a group does not defer them); with a vendor library the group
-// calls are forwarded so grouped vendor operations (send/recv) keep their semantics (nccl.cc:823-838).
-ncclResult_t ncclGroupStart(void) { return vendorNccl() ? vendorNccl()->GroupStart() : ncclSuccess; }
-ncclResult_t ncclGroupEnd(void) { return vendorNccl() ? vendorNccl()->GroupEnd() : ncclSuccess; }
+// Native collectives run when called (a group does not defer them); native Send / Recv issued inside
+// a group are queued and run at the outermost ncclGroupEnd (nccl_compat.cpp: groupStart / groupEnd).
+// With a vendor library the group calls are forwarded as well, so grouped vendor operations keep
+// their semantics (nccl.cc:823-838).
+ncclResult_t ncclGroupStart(void) { return (ncclResult_t)groupStart(); }
+ncclResult_t ncclGroupEnd(void) { return (ncclResult_t)groupEnd(); }
 
 ncclResult_t ncclMemAlloc(void** ptr, size_t size) {
   return (ncclResult_t)guarded([&] {

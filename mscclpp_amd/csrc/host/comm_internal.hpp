@@ -38,6 +38,9 @@ int alltoallDefaultBlocks(uint64_t maxRecvBytes);
 int launchReduce(const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes, int dtype, int op, int root,
                  int nblocks, int nthreads, uint64_t budget, hipStream_t s);
 int reduceDefaultBlocks(uint64_t bytes);
+int launchSendRecv(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdSendRecvOp* ops, int nops,
+                   int nblocks, int nthreads, uint64_t budget, hipStream_t s);
+int sendrecvDefaultBlocks(uint64_t bytes);
 size_t ll16ScratchRequired(int nranks, size_t bytes, int dtype);
 size_t ll8ScratchRequired(int nranks, size_t bytes, int dtype);
 size_t testLLScratchRequired(int nranks, size_t bytes);
@@ -722,6 +725,110 @@ struct ncclComm {
     return rc;
   }
 
+  // ---- Send / Recv by a zero-copy pull (kernels/sendrecv.hip) ------------------
+  // Point-to-point, so nothing here is collective.  A send exports its buffer's allocation and
+  // posts {blob, bytes, ok} to the peer through the bootstrap mailbox (never waiting for the peer);
+  // a receive takes the oldest such message from that peer (the mailbox is FIFO per source and tag,
+  // so the k-th receive matches the k-th send), imports the allocation and pulls.  One kernel per
+  // (communicator, stream) then runs the operations of a call, or of a whole group, in call order.
+  static constexpr int kP2pTag = 3;  // outside the 4k+0..2 tag spaces of core.cpp (memTag, connTag, semTag)
+  struct P2pMsg {
+    IpcBlob blob;    // the allocation holding the send buffer; blob.offset = the buffer inside it
+    uint64_t bytes;
+    uint32_t ok;     // 0: the sender could not export its buffer; both sides refuse the transfer
+    uint32_t pad;
+  };
+  // Imports of the peers' send allocations, kept open per peer so that a second transfer from the
+  // same allocation opens nothing: at most kP2pKept per peer, the least recently used one retired
+  // beyond that, behind the events of the launches that read through it (as bcastMaps / bcastUses).
+  // A launch holds at most MSCCLPP_AMD_SENDRECV_MAX_OPS <= kP2pKept mappings, so the one retired is
+  // never one the pending launch uses.
+  static constexpr size_t kP2pKept = 64;
+  struct P2pImport {
+    std::shared_ptr<void> map;
+    UseEvents uses;
+    uint64_t lastUse = 0;
+  };
+  std::array<std::vector<P2pImport>, MSCCLPP_AMD_MAX_RANKS> p2pImports;
+
+  // Post a send's message; false (with ok = 0 posted) when the buffer cannot be exported.
+  // (No communicator state is touched: the bootstrap serialises its own socket.)
+  bool p2pPost(const void* send, uint64_t bytes, int peer) {
+    P2pMsg msg{};
+    msg.bytes = bytes;
+    try {
+      msg.blob = exportBlob(send);
+      msg.ok = 1;
+    } catch (const std::exception& e) {  // e.g. host memory: the peer still gets its message
+      warn(std::string("ncclSend: the buffer cannot be exported: ") + e.what());
+      (void)hipGetLastError();
+      msg.blob = IpcBlob{};
+    }
+    boot->send(&msg, sizeof(msg), peer, kP2pTag);
+    return msg.ok != 0;
+  }
+
+  // Match a receive with the peer's oldest posted send: the sender's buffer as mapped here, or null
+  // when the sender refused or announced another byte count (nothing may be launched for it).
+  // *mapping: the import it lies in, for p2pLaunch.
+  const void* p2pMatch(uint64_t bytes, int peer, void** mapping) {
+    P2pMsg msg{};
+    boot->recv(&msg, sizeof(msg), peer, kP2pTag);  // (outside mu: this waits for the peer's call)
+    std::lock_guard<std::mutex> lk(mu);
+    if (!msg.ok) {
+      warn("ncclRecv: rank " + std::to_string(peer) + " could not export its send buffer");
+      return nullptr;
+    }
+    if (msg.bytes != bytes) {
+      warn("ncclRecv: rank " + std::to_string(peer) + " sends " + std::to_string(msg.bytes) + " bytes, " +
+           std::to_string(bytes) + " expected (its kernel ends at the spin budget)");
+      return nullptr;
+    }
+    auto m = importBlob(msg.blob);
+    auto& kept = p2pImports[(size_t)peer];
+    auto it = std::find_if(kept.begin(), kept.end(), [&](const P2pImport& i) { return i.map == m; });
+    if (it == kept.end()) {
+      if (kept.size() >= kP2pKept) {
+        auto lru = std::min_element(kept.begin(), kept.end(),
+                                    [](const P2pImport& x, const P2pImport& y) { return x.lastUse < y.lastUse; });
+        Retired r;
+        r.maps.push_back(std::move(lru->map));
+        r.uses = std::move(lru->uses);
+        retired.push_back(std::move(r));
+        kept.erase(lru);
+      }
+      kept.emplace_back();
+      it = kept.end() - 1;
+      it->map = m;
+    }
+    it->lastUse = ++useClock;
+    *mapping = m.get();
+    return (const char*)m.get() + msg.blob.offset;
+  }
+
+  // One kernel for the operations of this rank on `stream`, in call order (`send` of a receive =
+  // what p2pMatch returned; used: the (peer, mapping) pairs its receives read through).
+  int p2pLaunch(const mscclppAmdSendRecvOp* ops, int nops, const std::vector<std::pair<int, void*>>& used,
+                hipStream_t stream) {
+    std::lock_guard<std::mutex> lk(mu);
+    mscclppAmdRankView v = baseView(nullptr, nullptr);
+    const int rc = launchSendRecv(&v, 1, nranks, ops, nops, 0, 0, spinBudgetTicks(), stream);
+    if (rc == 0)
+      for (const auto& t : used)
+        for (auto& i : p2pImports[(size_t)t.first])
+          if (i.map.get() == t.second) i.uses.record(stream, device);
+    flushRetired();
+    return rc;
+  }
+
+  void dropP2pImports() {
+    for (auto& kept : p2pImports) {
+      for (auto& i : kept)
+        for (auto& e : i.uses.ev) (void)hipEventDestroy(e.second);
+      kept.clear();
+    }
+  }
+
   // AllToAllv's send buffers.  Its ranks pass buffers of different sizes, which each rank's
   // allocator places on its own, so "my buffer X goes with your buffer Y" -- what userRegs caches,
   // keyed by the local buffer alone -- does not hold from one call to the next.  The call's own
@@ -808,6 +915,7 @@ struct ncclComm {
     bcastUses = {};
     bcastCaptured = {};
     bcastPinned.clear();
+    dropP2pImports();
     clearRetired();
     boot->barrier();
   }
@@ -982,6 +1090,7 @@ struct ncclComm {
       for (auto& e : u.ev) (void)hipEventDestroy(e.second);
     bcastUses = {};
     bcastPinned.clear();
+    dropP2pImports();
     peerLL = peerBulk = peerTok = PeerBufs();
     clearRetired();
     freeDevice(llScratch);
@@ -1030,12 +1139,16 @@ struct VendorNccl {
 // The vendor library named by MSCCLPP_AMD_NCCL_LIB_PATH (or MSCCLPP_NCCL_LIB_PATH), or null.
 const VendorNccl* vendorNccl();
 // MSCCLPP_AMD_FORCE_NCCL_FALLBACK_OPERATION ("all" or a comma list of allreduce, allgather,
-// reducescatter, broadcast, alltoall, alltoallv, reduce) names `op`: a whole list entry equals it, so
-// "reducescatter" does not name "reduce".
+// reducescatter, broadcast, alltoall, alltoallv, reduce, sendrecv) names `op`: a whole list entry
+// equals it, so "reducescatter" does not name "reduce".
 bool forcedFallback(const char* op);
 // ncclCommInitRank with the bootstrap's connect / receive timeout given (ncclCommInitRank takes it
 // from MSCCLPP_AMD_BOOTSTRAP_TIMEOUT_S); commId is the 128-byte unique id.  Returns an ncclResult_t.
 int commInitRank(ncclComm_t* comm, int nranks, const void* commId, int rank, int timeoutSec);
+// ncclGroupStart / ncclGroupEnd: a thread-local depth; the native Send / Recv queued meanwhile run at
+// the outermost end.  Both forward to the vendor library when one is loaded.  ncclResult_t values.
+int groupStart();
+int groupEnd();
 void initFallbackComm(ncclComm* c);                 // collective over c's bootstrap
 void destroyFallbackComm(ncclComm* c, bool abort);
 }  // namespace host

@@ -5,16 +5,19 @@
 //    ncclAllToAllv (zero-copy pull from every peer, kernels/alltoall.hip; the reference leaves both
 //    to the vendor library, nccl.cc:794-821), ncclReduce (zero-copy pull-reduce at the root,
 //    kernels/reduce.hip, for the data types and operations AllReduce carries; the reference returns
-//    ncclInternalError without a vendor library, nccl.cc:521-542), ncclCommSplit (nccl.cc:405-435),
+//    ncclInternalError without a vendor library, nccl.cc:521-542), ncclSend / ncclRecv between two
+//    different ranks, alone or inside ncclGroupStart / ncclGroupEnd (zero-copy pull by the receiver,
+//    kernels/sendrecv.hip; the reference: nccl.cc:774-792), ncclCommSplit (nccl.cc:405-435),
 //    ncclCommInitRankScalable with one id, ncclCommRegister / Deregister and ncclCommWindowRegister /
 //    Deregister (the path registers buffers lazily on first use, so these only hand the pointer back);
 //  * forwarded to the vendor library when MSCCLPP_AMD_NCCL_LIB_PATH (or the reference's
 //    MSCCLPP_NCCL_LIB_PATH) names it -- the reference's dlopen fallback, nccl.cc:72-160, :323-346:
-//    ncclSend/Recv, ncclRedOpCreatePreMulSum/Destroy, ncclGroupSimulateEnd, group calls,
-//    and AllReduce / AllGather / ReduceScatter / Broadcast / AllToAll(v) / Reduce for data types and
-//    operations this path does not carry or that MSCCLPP_AMD_FORCE_NCCL_FALLBACK_OPERATION
-//    (reference: MSCCLPP_FORCE_NCCL_FALLBACK_OPERATION, "all" or a comma list; keys alltoall,
-//    alltoallv and reduce for the three above) forces there.  Without a vendor library the operations not
+//    ncclSend/Recv to oneself, ncclRedOpCreatePreMulSum/Destroy, ncclGroupSimulateEnd, group calls
+//    (beside the native group queue), and AllReduce / AllGather / ReduceScatter / Broadcast /
+//    AllToAll(v) / Reduce / Send / Recv for data types and operations this path does not carry or
+//    that MSCCLPP_AMD_FORCE_NCCL_FALLBACK_OPERATION (reference:
+//    MSCCLPP_FORCE_NCCL_FALLBACK_OPERATION, "all" or a comma list; keys alltoall, alltoallv, reduce
+//    and sendrecv for the four above) forces there.  Without a vendor library the operations not
 //    carried here return ncclInternalError, as the reference does for the same cases.
 #include <dlfcn.h>
 #include <sys/stat.h>
@@ -150,6 +153,119 @@ static bool rangesOverlap(const void* a, size_t na, const void* b, size_t nb) {
   return x < y + nb && y < x + na;
 }
 
+// ---- Send / Recv and group calls -----------------------------------------------------------------
+// A byte move by the zero-copy pull kernel (kernels/sendrecv.hip, ncclComm::p2pPost / p2pMatch /
+// p2pLaunch).  A call outside a group is a group of one.  At the outermost ncclGroupEnd all sends
+// are posted first (a post never waits for the peer), then all receives are matched (each waits for
+// the peer's post only), then one kernel per (communicator, stream) runs that pair's operations in
+// call order.  A transfer that one side refuses (a send buffer that cannot be exported, which the
+// receiver learns from the message; a byte count that differs, which only the receiver sees) is
+// left out of the table and the call returns ncclInvalidArgument; the rest of the group still runs.
+namespace {
+struct QueuedP2p {
+  ncclComm_t comm;
+  void* stream;
+  bool send;
+  const void* sbuf;  // a send's buffer; a receive's: the sender's buffer as mapped here, once matched
+  void* rbuf;
+  uint64_t bytes;
+  int peer;
+  void* mapping = nullptr;
+  bool dropped = false;
+};
+thread_local int gGroupDepth = 0;
+thread_local std::vector<QueuedP2p> gGroupQueue;
+
+int flushP2p() {
+  std::vector<QueuedP2p> q;
+  q.swap(gGroupQueue);
+  // more operations than one kernel's table holds: refused before anything is posted (splitting a
+  // group over several kernels can deadlock: the peers' tables would not line up)
+  for (size_t i = 0; i < q.size(); ++i) {
+    size_t same = 0;
+    for (const auto& o : q) same += o.comm == q[i].comm && o.stream == q[i].stream;
+    if (same > MSCCLPP_AMD_SENDRECV_MAX_OPS) {
+      warn("a group holds " + std::to_string(same) + " Send / Recv operations on one communicator and stream; at most " +
+           std::to_string(MSCCLPP_AMD_SENDRECV_MAX_OPS) + " are carried");
+      return (int)ncclInvalidUsage;
+    }
+  }
+  int result = ncclSuccess;
+  for (auto& o : q)
+    if (o.send && !o.comm->p2pPost(o.sbuf, o.bytes, o.peer)) {
+      o.dropped = true;
+      result = ncclInvalidArgument;
+    }
+  for (auto& o : q)
+    if (!o.send) {
+      o.sbuf = o.comm->p2pMatch(o.bytes, o.peer, &o.mapping);
+      if (!o.sbuf) {
+        o.dropped = true;
+        result = ncclInvalidArgument;
+      }
+    }
+  std::vector<bool> launched(q.size(), false);
+  for (size_t i = 0; i < q.size(); ++i) {
+    if (launched[i]) continue;
+    std::vector<mscclppAmdSendRecvOp> ops;
+    std::vector<std::pair<int, void*>> used;
+    for (size_t j = i; j < q.size(); ++j) {
+      const QueuedP2p& o = q[j];
+      if (o.comm != q[i].comm || o.stream != q[i].stream) continue;
+      launched[j] = true;
+      if (o.dropped) continue;
+      const int me = o.comm->rank;
+      ops.push_back({o.send ? me : o.peer, o.send ? o.peer : me, o.sbuf, o.rbuf, o.bytes});
+      if (!o.send) used.emplace_back(o.peer, o.mapping);
+    }
+    if (ops.empty()) continue;
+    const int rc = q[i].comm->p2pLaunch(ops.data(), (int)ops.size(), used, (hipStream_t)q[i].stream);
+    if (rc != 0 && result == ncclSuccess) result = rc;
+  }
+  return result;
+}
+
+int p2pCall(bool send, const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, int peer,
+            ncclComm_t comm, void* stream) {
+  if (!comm) return (int)ncclInvalidArgument;
+  if (count == 0) return (int)ncclSuccess;  // no exchange, no launch (on both sides: the counts match)
+  if (peer < 0 || peer >= comm->nranks) return (int)ncclInvalidArgument;
+  const size_t tb = ncclTypeBytes(datatype);
+  const char* what = send ? "ncclSend" : "ncclRecv";
+  // to oneself (every call on a one-rank communicator included) is not carried
+  if (peer == comm->rank || forcedFallback("sendrecv")) {
+    if (vendorComm(comm) && vendorNccl()->Send && vendorNccl()->Recv)
+      return send ? (int)vendorNccl()->Send(sendbuff, count, datatype, peer, vendorComm(comm), stream)
+                  : (int)vendorNccl()->Recv(recvbuff, count, datatype, peer, vendorComm(comm), stream);
+    if (peer == comm->rank) return (int)unavailable(what);
+  }
+  if (tb == 0 || (send ? !sendbuff : !recvbuff)) return (int)ncclInvalidArgument;
+  if (ncclComm::capturing((hipStream_t)stream)) {
+    warn(std::string(what) + " exchanges a message between the hosts on every call, which a captured graph cannot replay");
+    return (int)ncclInvalidUsage;
+  }
+  QueuedP2p o{comm, stream, send, sendbuff, recvbuff, (uint64_t)count * tb, peer};
+  gGroupQueue.push_back(o);
+  return gGroupDepth > 0 ? (int)ncclSuccess : flushP2p();
+}
+}  // namespace
+
+namespace mscclpp_amd {
+namespace host {
+int groupStart() {
+  ++gGroupDepth;
+  return vendorNccl() ? (int)vendorNccl()->GroupStart() : (int)ncclSuccess;
+}
+
+int groupEnd() {
+  int result = ncclSuccess;
+  if (gGroupDepth > 0 && --gGroupDepth == 0 && !gGroupQueue.empty()) result = guarded([&] { return flushP2p(); });
+  const int vr = vendorNccl() ? (int)vendorNccl()->GroupEnd() : (int)ncclSuccess;
+  return result != ncclSuccess ? result : vr;
+}
+}  // namespace host
+}  // namespace mscclpp_amd
+
 extern "C" {
 
 ncclResult_t ncclBroadcast(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, int root,
@@ -248,17 +364,11 @@ ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, nccl
 
 ncclResult_t ncclSend(const void* sendbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm,
                       void* stream) {
-  if (!comm) return ncclInvalidArgument;
-  if (vendorComm(comm) && vendorNccl()->Send)
-    return vendorNccl()->Send(sendbuff, count, datatype, peer, vendorComm(comm), stream);
-  return unavailable("ncclSend");
+  return (ncclResult_t)guarded([&] { return p2pCall(true, sendbuff, nullptr, count, datatype, peer, comm, stream); });
 }
 
 ncclResult_t ncclRecv(void* recvbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm, void* stream) {
-  if (!comm) return ncclInvalidArgument;
-  if (vendorComm(comm) && vendorNccl()->Recv)
-    return vendorNccl()->Recv(recvbuff, count, datatype, peer, vendorComm(comm), stream);
-  return unavailable("ncclRecv");
+  return (ncclResult_t)guarded([&] { return p2pCall(false, nullptr, recvbuff, count, datatype, peer, comm, stream); });
 }
 
 ncclResult_t ncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, ncclComm_t comm,
@@ -513,5 +623,36 @@ int mscclppAmdReduceLaunch(const mscclppAmdRankView* views, int nviews, int nran
                                      budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream);
   });
 }
+
+// Send / Recv for in-process ranks (and the one-view form ncclSend / ncclRecv launch): everything is
+// checked before a device is touched; a refusal launches nothing.
+int mscclppAmdSendRecvLaunch(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdSendRecvOp* ops,
+                             int nops, int nblocks, int nthreads, uint64_t budgetTicks, void* stream) {
+  return guarded([&] {
+    if (!views || !ops || nviews < 1 || nranks < 2 || nranks > MSCCLPP_AMD_MAX_RANKS) return (int)ncclInvalidArgument;
+    if (nviews != 1 && nviews != nranks) return (int)ncclInvalidArgument;
+    if (nops < 1 || nops > MSCCLPP_AMD_SENDRECV_MAX_OPS) return (int)ncclInvalidArgument;
+    for (int i = 0; i < nviews; ++i) {
+      const mscclppAmdRankView& v = views[i];
+      if (!v.tokens || !v.expected || !v.err) return (int)ncclInvalidArgument;
+      if (v.rank < 0 || v.rank >= nranks) return (int)ncclInvalidArgument;
+      for (int q = 0; q < nranks; ++q)
+        if (!v.peerTokens[q]) return (int)ncclInvalidArgument;
+    }
+    for (int i = 0; i < nops; ++i) {
+      const mscclppAmdSendRecvOp& o = ops[i];
+      if (o.src < 0 || o.src >= nranks || o.dst < 0 || o.dst >= nranks || o.src == o.dst || o.bytes == 0)
+        return (int)ncclInvalidArgument;
+      // the receiving view dereferences both pointers, a sending view neither
+      bool received = false;
+      for (int k = 0; k < nviews; ++k) received = received || views[k].rank == o.dst;
+      if (received && (!o.send || !o.recv)) return (int)ncclInvalidArgument;
+    }
+    return mscclpp_amd::launchSendRecv(views, nviews, nranks, ops, nops, nblocks, nthreads,
+                                       budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream);
+  });
+}
+
+int mscclppAmdSendRecvDefaultBlocks(uint64_t bytes) { return mscclpp_amd::sendrecvDefaultBlocks(bytes); }
 
 }  // extern "C"

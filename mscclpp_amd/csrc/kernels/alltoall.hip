@@ -26,6 +26,7 @@
 #include <mutex>
 
 #include "common.hpp"
+#include "copy_range.hpp"
 #include "handshake.hpp"
 
 namespace mscclpp_amd {
@@ -64,61 +65,6 @@ static_assert(sizeof(mscclppAmdRankView) == 336, "Views<kMaxRanks> is sized agai
 static_assert(sizeof(A2AArgs<1>) <= kKernargLimit, "one-view AllToAll arguments exceed the kernel-argument limit");
 static_assert(sizeof(A2AArgs<kMaxRanks>) <= kKernargLimit, "in-process AllToAll arguments exceed the kernel-argument limit");
 static_assert(sizeof(A2ATableArg) + 16 <= kKernargLimit, "the staged segment table exceeds the kernel-argument limit");
-
-template <int Policy, int W>
-__device__ __forceinline__ void copy_narrow(const uint8_t* src, uint8_t* dst, uint64_t nUnits, uint32_t tid, uint32_t T) {
-  const auto rs = make_rsrc(src);
-  const auto rd = make_rsrc(dst);
-  for (uint64_t u = tid; u < nUnits; u += T) {  // (64-bit: nUnits may sit within T of 2^32)
-    const uint32_t off = (uint32_t)(u * W);
-    if constexpr (W == 8)
-      store8<kPlain>(rd, off, load8<Policy>(rs, off));
-    else if constexpr (W == 4)
-      store4<kPlain>(rd, off, load4<Policy>(rs, off));
-    else if constexpr (W == 2)
-      __builtin_amdgcn_raw_buffer_store_b16(__builtin_amdgcn_raw_buffer_load_b16(rs, off, 0, Policy), rd, off, 0, kPlain);
-    else
-      __builtin_amdgcn_raw_buffer_store_b8(__builtin_amdgcn_raw_buffer_load_b8(rs, off, 0, Policy), rd, off, 0, kPlain);
-  }
-}
-
-// dst[0, len) = src[0, len); len <= kBlkOffsetLimit (one buffer resource each, rebased here).
-template <int Policy, int U>
-__device__ __forceinline__ void copy_range(const uint8_t* src, uint8_t* dst, uint64_t len, uint32_t tid, uint32_t T) {
-  const uint32_t mis = ((uint32_t)(uintptr_t)src | (uint32_t)(uintptr_t)dst) & 15u;
-  uint64_t done;
-  if (mis == 0) {
-    const auto rs = make_rsrc(src);
-    const auto rd = make_rsrc(dst);
-    const uint32_t nUnits = (uint32_t)(len / 16);
-    for (uint32_t u0 = tid; u0 < nUnits; u0 += T * U) {
-      u32x4 w[U];
-#pragma unroll
-      for (int k = 0; k < U; ++k) {
-        const uint32_t u = u0 + k * T;
-        if (u < nUnits) w[k] = load16<Policy>(rs, u * 16u);
-      }
-#pragma unroll
-      for (int k = 0; k < U; ++k) {
-        const uint32_t u = u0 + k * T;
-        if (u < nUnits) store16<kPlain>(rd, u * 16u, w[k]);
-      }
-    }
-    done = (uint64_t)nUnits * 16;
-  } else if (mis & 1u) {
-    done = 0;
-  } else if (mis & 2u) {
-    copy_narrow<Policy, 2>(src, dst, len / 2, tid, T);
-    done = len & ~1ull;
-  } else if (mis & 4u) {
-    copy_narrow<Policy, 4>(src, dst, len / 4, tid, T);
-    done = len & ~3ull;
-  } else {
-    copy_narrow<Policy, 8>(src, dst, len / 8, tid, T);
-    done = len & ~7ull;
-  }
-  if (done < len) copy_narrow<Policy, 1>(src + done, dst + done, len - done, tid, T);
-}
 
 template <int NV, int U>
 __global__ void __launch_bounds__(512) alltoallKernel(A2AArgs<NV> a) {
