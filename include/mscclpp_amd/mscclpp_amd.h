@@ -54,6 +54,11 @@ enum {
   MSCCLPP_AMD_NUM_DTYPES = 15
 };
 enum { MSCCLPP_AMD_SUM = 0, MSCCLPP_AMD_MIN = 1 };
+/* ncclMax / ncclAvg: accepted ONLY by mscclppAmdPullReduceLaunch (and through it by ncclAllReduce /
+ * ncclReduceScatter / ncclReduce); every other entry point keeps the op range SUM .. MIN. */
+enum { MSCCLPP_AMD_MAX = 2, MSCCLPP_AMD_AVG = 3 };
+/* the collectives of mscclppAmdPullReduceLaunch */
+enum { MSCCLPP_AMD_PULL_REDUCE = 0, MSCCLPP_AMD_PULL_REDUCE_SCATTER = 1, MSCCLPP_AMD_PULL_ALLREDUCE = 2 };
 
 /* AllReduce algorithms (names follow the reference's AlgorithmCollection keys) */
 enum {
@@ -206,6 +211,26 @@ int mscclppAmdAllToAllLaunch(const mscclppAmdRankView* views, int nviews, int nr
  * workgroup's range exceeds 4 GiB (more workgroups carry it), or the grid cannot be resident at once. */
 int mscclppAmdReduceLaunch(const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes, int dtype, int op,
                            int root, int nblocks, int nthreads, uint64_t budgetTicks, void* stream);
+/* ncclMax / ncclAvg of Reduce, ReduceScatter and AllReduce by one zero-copy pull-reduce kernel
+ * (kernels/pull_reduce.hip; arithmetic: pull_reduce_device.hpp).  Operands are taken in rank order
+ * 0 .. n - 1 whichever rank reduces an element, so the three collectives give the same bits for
+ * the same inputs.  coll MSCCLPP_AMD_PULL_REDUCE: `bytes` of every input reduced into the root's
+ * output (other outputs untouched, may be NULL); _REDUCE_SCATTER: inputs hold nranks * bytes, rank
+ * q's output receives block q (bytes); _ALLREDUCE: every output receives the `bytes` reduced -- rank
+ * q reduces slice q (ceil(bytes / nranks) rounded up to 16) and the ranks then copy one another's
+ * slices out of peerOutput[q].  Views as for mscclppAmdReduceLaunch, plus peerOutput[q] for
+ * AllReduce.  In place is carried as input == output (Reduce on the root, AllReduce) and output ==
+ * input + rank * bytes (ReduceScatter); the caller rules out any other overlap.  op: MSCCLPP_AMD_MAX
+ * or MSCCLPP_AMD_AVG; dtype: F16, BF16, F32, I32, U32, U8, E4M3, E5M2; pointers need the element's
+ * alignment only.  root is read for Reduce only.  nblocks <= 0: mscclppAmdPullReduceDefaultBlocks,
+ * a function of (coll, bytes) alone; every rank of one collective must launch the same nblocks.
+ * 4 (nothing is launched, no device is touched): SUM / MIN (they have their own kernels), any
+ * other dtype code, a byte count of 0 or one that splits an element, a bad root, coll or launch
+ * shape, null fields; 5: a workgroup's range exceeds 4 GiB (more workgroups carry it), or the grid
+ * cannot be resident at once. */
+int mscclppAmdPullReduceLaunch(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes, int dtype,
+                               int op, int root, int nblocks, int nthreads, uint64_t budgetTicks, void* stream);
+int mscclppAmdPullReduceDefaultBlocks(int coll, uint64_t bytes);
 /* Send / Recv by a zero-copy pull (kernels/sendrecv.hip): one launch runs a table of point-to-point
  * operations, in table order.  An operation moves `bytes` from `send` on rank `src` to `recv` on
  * rank `dst`: the receiver reads `send` -- the address at which the view of rank `dst` has the
@@ -262,8 +287,9 @@ int mscclppAmdTunedConfigSource(const char* collective, int nranks, size_t bytes
 // all-gather stores issued, 3 end; LL16: 0 start, 1 step 1 (puts), 2 step 2 (reduce + broadcast),
 // 3 step 3 (unpack) done; LL8: 0 start, 1 puts issued, 2 end; AllToAll: 0 start, 1 entry handshake
 // done, 2 segments stored, 3 end; Reduce: 0 start, 1 entry handshake done, 2 result stored (root),
-// 3 end; Send/Recv: 0 start, 1 readies posted, 2 receives stored, 3 dones seen.  buf = NULL turns it
-// off.  Returns 0,
+// 3 end; Send/Recv: 0 start, 1 readies posted, 2 receives stored, 3 dones seen; pull-reduce (MAX /
+// AVG): 0 start, 1 entry handshake done, 2 own range reduced, 3 peers' slices gathered (AllReduce
+// only), 4 end.  buf = NULL turns it off.  Returns 0,
 // or 4 when the buffer is too small.
 #define MSCCLPP_AMD_TRACE_BYTES ((size_t)MSCCLPP_AMD_MAX_RANKS * 256 * 8 * 8)
 int mscclppAmdTraceSet(void* buf, size_t bytes);

@@ -1,0 +1,199 @@
+// ncclMax / ncclAvg arithmetic of the pull-reduce kernel (kernels/pull_reduce.hip), over packed
+// 32-bit words.  The reference carries SUM and MIN only (reduce_device.hpp restates those bit for
+// bit), so these two are defined here, not restated:
+//
+//  * operands are taken in RANK order 0, 1, ..., n - 1 on whichever rank computes the element, so
+//    Reduce, ReduceScatter and AllReduce of the same inputs give the same bits;
+//  * MAX, float types: every element decodes exactly to fp32; acc = x_0, then for k = 1 .. n - 1
+//    `if (isnan(acc) || x_k > acc) acc = x_k`.  The result is the raw bits of the winning element --
+//    a selection, never re-encoded: NaN only if every rank's element is NaN (then rank n - 1's bits),
+//    and of equal values (+0 / -0) the lowest rank's bits;
+//  * MAX, integers: signed compare for int32, unsigned for uint32 and uint8;
+//  * AVG, float types: s = the fp32 sum of the decoded elements in rank order (one RNE add each),
+//    r = s * inv_n with inv_n = 1.0f / (float)n computed by the host, and r rounded ONCE to the
+//    element type: fp32 as is, (_Float16)r, (__bf16)r (RNE, none of the SUM path's clipping),
+//    fp8x4_encode (saturating, RNE);
+//  * AVG, integers: the exact sum (int64 / uint64 / uint32 for int32 / uint32 / uint8) divided by n,
+//    truncating toward zero.
+#pragma once
+
+#include "reduce_device.hpp"
+
+namespace mscclpp_amd {
+
+// Operation codes of the pull-reduce path only (MSCCLPP_AMD_MAX / MSCCLPP_AMD_AVG); the <DT, OP>
+// kernels of ROp keep their range.
+enum PullOp : int { kPullMax = 2, kPullAvg = 3 };
+
+// The reduce types the path carries: the eight element types, accumulated as defined above.
+__host__ __device__ constexpr bool pull_reduce_carries(int dt) {
+  return dt == kF16 || dt == kBF16 || dt == kF32 || dt == kI32 || dt == kU32 || dt == kE4M3 || dt == kE5M2 || dt == kU8;
+}
+
+__device__ __forceinline__ bool max_takes(float acc, float x) { return acc != acc || x > acc; }
+
+__device__ __forceinline__ float f16_to_f32(uint32_t h) { return (float)__builtin_bit_cast(_Float16, (uint16_t)h); }
+
+// Divide by the rank count (2 .. 8): constant divisors, so no 64-bit software divide per element.
+template <typename T>
+__device__ __forceinline__ T div_ranks(T s, int n) {
+  switch (n) {
+    case 2: return s / 2;
+    case 3: return s / 3;
+    case 4: return s / 4;
+    case 5: return s / 5;
+    case 6: return s / 6;
+    case 7: return s / 7;
+    default: return s / 8;
+  }
+}
+
+// The fp32 product of the float AVG as a value of its own.  Without this, `(_Float16)(s * inv)` is
+// selected as one v_fma_mixlo_f16 (also under `#pragma clang fp contract(off)`), which rounds the
+// exact product straight to fp16 instead of to fp32 first, and adds +0, which turns -0 into +0.
+// (An empty asm statement: no instruction, only the register constraint.)
+__device__ __forceinline__ float fp32_product(float s, float inv) {
+  float r = s * inv;
+  asm("" : "+v"(r));
+  return r;
+}
+
+// One word's accumulator.  first(w): rank 0's word; next(w): the following rank's; word(n, inv_n):
+// the result.
+template <int DT, int OP>
+struct PullAcc;
+
+template <int DT>
+struct PullAcc<DT, kPullMax> {
+  uint32_t a;
+  __device__ __forceinline__ void first(uint32_t w) { a = w; }
+  __device__ __forceinline__ void next(uint32_t w) {
+    if constexpr (DT == kI32) {
+      a = (int32_t)w > (int32_t)a ? w : a;
+    } else if constexpr (DT == kU32) {
+      a = w > a ? w : a;
+    } else if constexpr (DT == kU8) {
+      uint32_t r = 0;
+#pragma unroll
+      for (int k = 0; k < 32; k += 8) {
+        const uint32_t x = (a >> k) & 0xffu, y = (w >> k) & 0xffu;
+        r |= (y > x ? y : x) << k;
+      }
+      a = r;
+    } else if constexpr (DT == kF32) {
+      a = max_takes(__builtin_bit_cast(float, a), __builtin_bit_cast(float, w)) ? w : a;
+    } else if constexpr (DT == kF16) {
+      const uint32_t m = (max_takes(f16_to_f32(a & 0xffffu), f16_to_f32(w & 0xffffu)) ? 0x0000ffffu : 0u) |
+                         (max_takes(f16_to_f32(a >> 16), f16_to_f32(w >> 16)) ? 0xffff0000u : 0u);
+      a = (w & m) | (a & ~m);
+    } else if constexpr (DT == kBF16) {
+      const uint32_t m = (max_takes(bf16_lo(a), bf16_lo(w)) ? 0x0000ffffu : 0u) |
+                         (max_takes(bf16_hi(a), bf16_hi(w)) ? 0xffff0000u : 0u);
+      a = (w & m) | (a & ~m);
+    } else {
+      const float4_t x = fp8x4_decode<DT == kE5M2>(a), y = fp8x4_decode<DT == kE5M2>(w);
+      const uint32_t m = (max_takes(x.x, y.x) ? 0x000000ffu : 0u) | (max_takes(x.y, y.y) ? 0x0000ff00u : 0u) |
+                         (max_takes(x.z, y.z) ? 0x00ff0000u : 0u) | (max_takes(x.w, y.w) ? 0xff000000u : 0u);
+      a = (w & m) | (a & ~m);
+    }
+  }
+  __device__ __forceinline__ uint32_t word(int, float) const { return a; }
+};
+
+template <>
+struct PullAcc<kF32, kPullAvg> {
+  float s;
+  __device__ __forceinline__ void first(uint32_t w) { s = __builtin_bit_cast(float, w); }
+  __device__ __forceinline__ void next(uint32_t w) {
+    s = s + __builtin_bit_cast(float, w);
+  }
+  __device__ __forceinline__ uint32_t word(int, float inv) const {
+    return __builtin_bit_cast(uint32_t, fp32_product(s, inv));
+  }
+};
+
+template <>
+struct PullAcc<kF16, kPullAvg> {
+  float lo, hi;
+  __device__ __forceinline__ void first(uint32_t w) {
+    lo = f16_to_f32(w & 0xffffu);
+    hi = f16_to_f32(w >> 16);
+  }
+  __device__ __forceinline__ void next(uint32_t w) {
+    lo = lo + f16_to_f32(w & 0xffffu);
+    hi = hi + f16_to_f32(w >> 16);
+  }
+  __device__ __forceinline__ uint32_t word(int, float inv) const {
+    const _Float16 l = (_Float16)fp32_product(lo, inv), h = (_Float16)fp32_product(hi, inv);
+    return (uint32_t)__builtin_bit_cast(uint16_t, l) | ((uint32_t)__builtin_bit_cast(uint16_t, h) << 16);
+  }
+};
+
+template <>
+struct PullAcc<kBF16, kPullAvg> {
+  float lo, hi;
+  __device__ __forceinline__ void first(uint32_t w) {
+    lo = bf16_lo(w);
+    hi = bf16_hi(w);
+  }
+  __device__ __forceinline__ void next(uint32_t w) {
+    lo = lo + bf16_lo(w);
+    hi = hi + bf16_hi(w);
+  }
+  __device__ __forceinline__ uint32_t word(int, float inv) const {
+    const __bf16 l = (__bf16)fp32_product(lo, inv), h = (__bf16)fp32_product(hi, inv);
+    return (uint32_t)__builtin_bit_cast(uint16_t, l) | ((uint32_t)__builtin_bit_cast(uint16_t, h) << 16);
+  }
+};
+
+template <int DT>
+struct PullAccFp8Avg {
+  float4_t s;
+  __device__ __forceinline__ void first(uint32_t w) { s = fp8x4_decode<DT == kE5M2>(w); }
+  __device__ __forceinline__ void next(uint32_t w) {
+    s = s + fp8x4_decode<DT == kE5M2>(w);
+  }
+  __device__ __forceinline__ uint32_t word(int, float inv) const {
+    return fp8x4_encode<DT == kE5M2>(
+        float4_t{fp32_product(s.x, inv), fp32_product(s.y, inv), fp32_product(s.z, inv), fp32_product(s.w, inv)});
+  }
+};
+template <>
+struct PullAcc<kE4M3, kPullAvg> : PullAccFp8Avg<kE4M3> {};
+template <>
+struct PullAcc<kE5M2, kPullAvg> : PullAccFp8Avg<kE5M2> {};
+
+template <>
+struct PullAcc<kI32, kPullAvg> {
+  int64_t s;
+  __device__ __forceinline__ void first(uint32_t w) { s = (int32_t)w; }
+  __device__ __forceinline__ void next(uint32_t w) { s += (int32_t)w; }
+  __device__ __forceinline__ uint32_t word(int n, float) const { return (uint32_t)(int32_t)div_ranks<int64_t>(s, n); }
+};
+
+template <>
+struct PullAcc<kU32, kPullAvg> {
+  uint64_t s;
+  __device__ __forceinline__ void first(uint32_t w) { s = w; }
+  __device__ __forceinline__ void next(uint32_t w) { s += w; }
+  __device__ __forceinline__ uint32_t word(int n, float) const { return (uint32_t)div_ranks<uint64_t>(s, n); }
+};
+
+template <>
+struct PullAcc<kU8, kPullAvg> {
+  uint32_t even, odd;  // two 16-bit sums each: bytes 0 and 2, bytes 1 and 3 (8 x 255 fits 11 bits)
+  __device__ __forceinline__ void first(uint32_t w) {
+    even = w & 0x00ff00ffu;
+    odd = (w >> 8) & 0x00ff00ffu;
+  }
+  __device__ __forceinline__ void next(uint32_t w) {
+    even += w & 0x00ff00ffu;
+    odd += (w >> 8) & 0x00ff00ffu;
+  }
+  __device__ __forceinline__ uint32_t word(int n, float) const {
+    return div_ranks<uint32_t>(even & 0xffffu, n) | (div_ranks<uint32_t>(odd & 0xffffu, n) << 8) |
+           (div_ranks<uint32_t>(even >> 16, n) << 16) | (div_ranks<uint32_t>(odd >> 16, n) << 24);
+  }
+};
+
+}  // namespace mscclpp_amd

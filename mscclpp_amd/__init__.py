@@ -25,6 +25,8 @@ E4M3, E5M2, E4M3_ACC_F16, E5M2_ACC_F16, E4M3_ACC_F32, E5M2_ACC_F32 = 5, 6, 7, 8,
 # uint8 tensors with accum=E4M3B15..., an explicit reduce-type code)
 U8, E4M3B15, E4M3B15_ACC_F16, E4M3B15_ACC_F32 = 11, 12, 13, 14
 SUM, MIN = 0, 1
+MAX, AVG = 2, 3  # InProcessRanks.pull_reduce only (ncclMax / ncclAvg: kernels/pull_reduce.hip)
+PULL_REDUCE, PULL_REDUCE_SCATTER, PULL_ALLREDUCE = 0, 1, 2
 ALGO_AUTO, ALGO_PACKET, ALGO_ALLPAIR, ALGO_FULLMESH, ALGO_RSAG, ALGO_RSAG_ZC, ALGO_RSAG_PIPELINE = 0, 1, 2, 3, 4, 5, 6
 ALGO_TEST_K2, ALGO_TEST_K5, ALGO_TEST_K6, ALGO_TEST_K7 = 102, 105, 106, 107  # mscclpp-test allreduce2/5/6/7 (int32)
 ALGO_NAMES = {"auto": 0, "packet": 1, "allpair": 2, "fullmesh": 3, "rsag": 4, "rsag_zc": 5, "rsag_pipeline": 6,
@@ -38,7 +40,7 @@ NCCL_DTYPES = {torch.float16: 6, torch.bfloat16: 9, torch.float32: 7, torch.int3
                torch.float8_e4m3fn: 10, torch.float8_e5m2: 11}
 # the byte-moving collectives carry every type with a size: the remaining ncclDataType_t values
 NCCL_MOVE_DTYPES = {torch.int8: 0, torch.int64: 4, torch.float64: 8}
-NCCL_OPS = {"sum": 0, "min": 3}
+NCCL_OPS = {"sum": 0, "min": 3, "max": 2, "avg": 4}
 DTYPE_CODES = {torch.float16: F16, torch.bfloat16: BF16, torch.float32: F32, torch.int32: I32, torch.uint8: U8,
                torch.float8_e4m3fn: E4M3, torch.float8_e5m2: E5M2}
 # accumulation dtype (ncclDataType_t) -> reduce-type code, for fp8 buffers
@@ -155,6 +157,8 @@ def lib():
         "mscclppAmdAllToAllLaunch": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(AllToAllSeg), i32, i32, u64, vp],
         "mscclppAmdReduceLaunch": [ctypes.POINTER(RankView), i32, i32, sz, i32, i32, i32, i32, i32, u64, vp],
         "ncclReduce": [vp, vp, sz, i32, i32, i32, vp, vp],
+        "mscclppAmdPullReduceLaunch": [ctypes.POINTER(RankView), i32, i32, i32, sz, i32, i32, i32, i32, i32, u64, vp],
+        "mscclppAmdPullReduceDefaultBlocks": [i32, u64],
         "mscclppAmdSendRecvLaunch": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(SendRecvOp), i32, i32, i32, u64, vp],
         "mscclppAmdSendRecvDefaultBlocks": [u64],
         "ncclSend": [vp, sz, i32, i32, vp, vp],
@@ -345,6 +349,8 @@ TRACE_PHASES = {
     "alltoall": ("entry_handshake", "pull", "exit_handshake"),
     "reduce": ("entry_handshake", "pull_reduce", "exit_handshake"),
     "sendrecv": ("post_ready", "pull", "wait_done"),
+    "pull_reduce": ("entry_handshake", "pull_reduce", "exit_handshake"),
+    "pull_allreduce": ("entry_handshake", "pull_reduce", "gather", "exit_handshake"),
 }
 
 
@@ -507,6 +513,25 @@ class InProcessRanks:
         code = lib().mscclppAmdReduceLaunch(arr, self.n, self.n, nbytes, dt, op, root, nblocks, nthreads, budget_ticks,
                                             stream_ptr(stream))
         check(code, "in-process reduce")
+
+    def pull_reduce(self, coll, inputs, outputs, op, root=0, nblocks=0, nthreads=0, budget_ticks=500_000_000,
+                    stream=None, accum=None):
+        """ncclMax / ncclAvg (op = MAX / AVG) for in-process ranks, operands in rank order.  coll
+        PULL_REDUCE: outputs[root] <- the reduction of inputs (outputs[r] may be None elsewhere);
+        PULL_REDUCE_SCATTER: inputs hold n blocks, outputs[r] <- block r reduced; PULL_ALLREDUCE: every
+        outputs[r] <- the reduction.  Flat tensors; views at any element offset are carried.  accum: a
+        reduce-type code for the buffers (U32 over int32 tensors)."""
+        dt = reduce_code(inputs[0].dtype, accum)
+        nbytes = inputs[0].numel() * inputs[0].element_size() // (self.n if coll == PULL_REDUCE_SCATTER else 1)
+        arr = self.views(inputs, [inputs[r] if o is None else o for r, o in enumerate(outputs)])
+        for r, o in enumerate(outputs):
+            if o is None:
+                arr[r].output = None
+                for q in range(self.n):
+                    arr[q].peerOutput[r] = None
+        code = lib().mscclppAmdPullReduceLaunch(arr, self.n, self.n, coll, nbytes, dt, op, root, nblocks, nthreads,
+                                                budget_ticks, stream_ptr(stream))
+        check(code, "in-process pull_reduce")
 
     def send_recv(self, ops, nblocks=0, nthreads=0, budget_ticks=500_000_000, stream=None):
         """ncclSend / ncclRecv (a whole group) for in-process ranks, one launch.  ops: (src, dst, send,

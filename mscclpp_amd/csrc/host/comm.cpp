@@ -465,11 +465,19 @@ ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, n
     }
     if (!sendbuff || !recvbuff || count == 0 || tb == 0) return (int)ncclInvalidArgument;  // nccl.cc:617-622
     const int dt = dtypeFromNccl(datatype);
-    const int o = opFromNccl(op);
-    if (comm->fallback && (dt < 0 || o < 0 || forcedFallback("allreduce")))  // nccl.cc:628-632
+    const int o = opFromNccl(op), po = pullOpFromNccl(op);
+    if (comm->fallback && (dt < 0 || (o < 0 && po < 0) || forcedFallback("allreduce")))  // nccl.cc:628-632
       return (int)vendorNccl()->AllReduce(sendbuff, recvbuff, count, datatype, op, (ncclComm_t)comm->fallback, stream);
+    if (dt >= 0 && po >= 0) {  // ncclMax / ncclAvg: the pull-reduce kernel (no Algorithm: no selector is asked)
+      if (sendbuff != recvbuff && bufferRangesOverlap(sendbuff, bytes, recvbuff, bytes)) {
+        warn("ncclAllReduce: the send and receive ranges overlap without being identical");
+        return (int)ncclInvalidArgument;
+      }
+      return comm->pullReduce(MSCCLPP_AMD_PULL_ALLREDUCE, sendbuff, recvbuff, bytes, dt, po, 0, (hipStream_t)stream);
+    }
     if (dt < 0 || o < 0) {
-      warn("unsupported dtype/op for AllReduce (supported: fp16, bf16, fp32, int32, uint32, uint8, fp8 e4m3/e5m2 x sum, min)");
+      warn("unsupported dtype/op for AllReduce (supported: fp16, bf16, fp32, int32, uint32, uint8, fp8 e4m3/e5m2 x sum, "
+           "min, max, avg)");
       return (int)ncclInvalidArgument;
     }
     return selectAndExecute(comm, "allreduce", sendbuff, recvbuff, bytes, bytes, bytes, datatype, op, stream);
@@ -488,10 +496,20 @@ ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recv
       return (int)ncclSuccess;
     }
     if (!sendbuff || !recvbuff || recvcount == 0 || tb == 0) return (int)ncclInvalidArgument;
-    const int dt = dtypeFromNccl(datatype), o = opFromNccl(op);
-    if (comm->fallback && (dt < 0 || o < 0 || forcedFallback("reducescatter")))  // nccl.cc:682-686
+    const int dt = dtypeFromNccl(datatype), o = opFromNccl(op), po = pullOpFromNccl(op);
+    if (comm->fallback && (dt < 0 || (o < 0 && po < 0) || forcedFallback("reducescatter")))  // nccl.cc:682-686
       return (int)vendorNccl()->ReduceScatter(sendbuff, recvbuff, recvcount, datatype, op, (ncclComm_t)comm->fallback,
                                               stream);
+    if (dt >= 0 && po >= 0) {  // ncclMax / ncclAvg: the pull-reduce kernel (no Algorithm: no selector is asked)
+      // in place is recv == send + rank * bytes: a lane stores only units it has loaded, and the
+      // peers read other blocks of the send buffer
+      const char* mine = (const char*)sendbuff + (size_t)comm->rank * bytes;
+      if (recvbuff != mine && bufferRangesOverlap(sendbuff, bytes * (size_t)comm->nranks, recvbuff, bytes)) {
+        warn("ncclReduceScatter: the receive range overlaps the send buffer elsewhere than at its own block");
+        return (int)ncclInvalidArgument;
+      }
+      return comm->pullReduce(MSCCLPP_AMD_PULL_REDUCE_SCATTER, sendbuff, recvbuff, bytes, dt, po, 0, (hipStream_t)stream);
+    }
     if (dt < 0 || o < 0) return (int)ncclInvalidArgument;
     const size_t total = bytes * (size_t)comm->nranks;  // messageSize = bytes * nRank (nccl.cc:692-697)
     return selectAndExecute(comm, "reducescatter", sendbuff, recvbuff, total, total, bytes, datatype, op, stream);

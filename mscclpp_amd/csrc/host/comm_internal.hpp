@@ -38,6 +38,9 @@ int alltoallDefaultBlocks(uint64_t maxRecvBytes);
 int launchReduce(const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes, int dtype, int op, int root,
                  int nblocks, int nthreads, uint64_t budget, hipStream_t s);
 int reduceDefaultBlocks(uint64_t bytes);
+int launchPullReduce(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes, int dtype, int op,
+                     int root, int nblocks, int nthreads, uint64_t budget, hipStream_t s);
+int pullReduceDefaultBlocks(int coll, uint64_t bytes);
 int launchSendRecv(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdSendRecvOp* ops, int nops,
                    int nblocks, int nthreads, uint64_t budget, hipStream_t s);
 int sendrecvDefaultBlocks(uint64_t bytes);
@@ -200,6 +203,17 @@ inline int opFromNccl(ncclRedOp_t op) {
   if (op == ncclSum) return MSCCLPP_AMD_SUM;
   if (op == ncclMin) return MSCCLPP_AMD_MIN;
   return -1;
+}
+// ncclMax / ncclAvg: the operations of the pull-reduce kernel (kernels/pull_reduce.hip), which is
+// no Algorithm of the collection; -1 for every other operation.
+inline int pullOpFromNccl(ncclRedOp_t op) {
+  if (op == ncclMax) return MSCCLPP_AMD_MAX;
+  if (op == ncclAvg) return MSCCLPP_AMD_AVG;
+  return -1;
+}
+inline bool bufferRangesOverlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + nb && y < x + na;
 }
 
 // MSCCLPP_NCCL_SYMMETRIC_MEMORY (env.hpp:101-107, env.cpp:67; any value but "0" is true): every rank
@@ -721,6 +735,26 @@ struct ncclComm {
     const auto ins = registerOutput(const_cast<void*>(send), stream);
     for (int r = 0; r < nranks; ++r) v.peerInput[r] = ins[r];
     const int rc = launchReduce(&v, 1, nranks, bytes, dtype, op, root, 0, 0, spinBudgetTicks(), stream);
+    recordUses(stream);
+    return rc;
+  }
+
+  // ncclMax / ncclAvg of Reduce, ReduceScatter and AllReduce (kernels/pull_reduce.hip; DESIGN.md
+  // §17d), the pattern of reduce(): the send buffer is what the peers read, so it is registered on
+  // every rank; an AllReduce's peers also read this rank's reduced slice out of its receive buffer,
+  // which is registered too (the same registration when in place).  bytes: the message of Reduce /
+  // AllReduce, the per-rank block of ReduceScatter.  Every rank derives the same grid from (coll, bytes).
+  int pullReduce(int coll, const void* send, void* recv, size_t bytes, int dtype, int op, int root, hipStream_t stream) {
+    std::lock_guard<std::mutex> lk(mu);
+    touched.clear();
+    mscclppAmdRankView v = baseView(send, recv);
+    const auto ins = registerOutput(const_cast<void*>(send), stream);
+    for (int r = 0; r < nranks; ++r) v.peerInput[r] = ins[r];
+    if (coll == MSCCLPP_AMD_PULL_ALLREDUCE) {
+      const auto outs = recv == send ? ins : registerOutput(recv, stream);
+      for (int r = 0; r < nranks; ++r) v.peerOutput[r] = outs[r];
+    }
+    const int rc = launchPullReduce(&v, 1, nranks, coll, bytes, dtype, op, root, 0, 0, spinBudgetTicks(), stream);
     recordUses(stream);
     return rc;
   }

@@ -353,9 +353,12 @@ ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, nccl
       warn("ncclReduce: the root's send and receive ranges overlap without being identical");
       return (int)ncclInvalidArgument;
     }
-    const int dt = dtypeFromNccl(datatype), o = opFromNccl(op);
-    if (vendorComm(comm) && vendorNccl()->Reduce && (dt < 0 || o < 0 || forcedFallback("reduce")))
+    const int dt = dtypeFromNccl(datatype), o = opFromNccl(op), po = pullOpFromNccl(op);
+    if (vendorComm(comm) && vendorNccl()->Reduce && (dt < 0 || (o < 0 && po < 0) || forcedFallback("reduce")))
       return (int)vendorNccl()->Reduce(sendbuff, recvbuff, count, datatype, op, root, vendorComm(comm), stream);
+    if (dt >= 0 && po >= 0)  // ncclMax / ncclAvg: the pull-reduce kernel, rank order (kernels/pull_reduce.hip)
+      return comm->pullReduce(MSCCLPP_AMD_PULL_REDUCE, sendbuff, isRoot ? recvbuff : nullptr, bytes, dt, po, root,
+                              (hipStream_t)stream);
     if (dt < 0 || o < 0) return (int)unavailable("ncclReduce of this data type or operation");
     // a non-root rank's recvbuff is ignored (and may be null)
     return comm->reduce(sendbuff, isRoot ? recvbuff : nullptr, bytes, dt, o, root, (hipStream_t)stream);
@@ -654,5 +657,38 @@ int mscclppAmdSendRecvLaunch(const mscclppAmdRankView* views, int nviews, int nr
 }
 
 int mscclppAmdSendRecvDefaultBlocks(uint64_t bytes) { return mscclpp_amd::sendrecvDefaultBlocks(bytes); }
+
+// ncclMax / ncclAvg of Reduce / ReduceScatter / AllReduce for in-process ranks (and the one-view
+// form the NCCL entry points launch): everything is checked before a device is touched; a refusal
+// launches nothing.
+int mscclppAmdPullReduceLaunch(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes, int dtype,
+                               int op, int root, int nblocks, int nthreads, uint64_t budgetTicks, void* stream) {
+  return guarded([&] {
+    if (!views || nviews < 1 || nranks < 2 || nranks > MSCCLPP_AMD_MAX_RANKS) return (int)ncclInvalidArgument;
+    if (nviews != 1 && nviews != nranks) return (int)ncclInvalidArgument;
+    if (coll < MSCCLPP_AMD_PULL_REDUCE || coll > MSCCLPP_AMD_PULL_ALLREDUCE) return (int)ncclInvalidArgument;
+    const bool reduce = coll == MSCCLPP_AMD_PULL_REDUCE, all = coll == MSCCLPP_AMD_PULL_ALLREDUCE;
+    if (reduce && (root < 0 || root >= nranks)) return (int)ncclInvalidArgument;
+    if (op != MSCCLPP_AMD_MAX && op != MSCCLPP_AMD_AVG) return (int)ncclInvalidArgument;  // SUM / MIN: their own kernels
+    if (bytes == 0) return (int)ncclInvalidArgument;  // (the dtype codes and a split element: launchPullReduce)
+    unsigned seen = 0;
+    for (int i = 0; i < nviews; ++i) {
+      const mscclppAmdRankView& v = views[i];
+      if (!v.input || !v.tokens || !v.expected || !v.err) return (int)ncclInvalidArgument;
+      if (v.rank < 0 || v.rank >= nranks || (seen >> v.rank) & 1u) return (int)ncclInvalidArgument;
+      seen |= 1u << v.rank;
+      for (int q = 0; q < nranks; ++q)
+        if (!v.peerTokens[q]) return (int)ncclInvalidArgument;
+      if (reduce && v.rank != root) continue;  // reads and writes no user memory
+      if (!v.output) return (int)ncclInvalidArgument;
+      for (int q = 0; q < nranks; ++q)
+        if (!v.peerInput[q] || (all && !v.peerOutput[q])) return (int)ncclInvalidArgument;
+    }
+    return mscclpp_amd::launchPullReduce(views, nviews, nranks, coll, bytes, dtype, op, root, nblocks, nthreads,
+                                         budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream);
+  });
+}
+
+int mscclppAmdPullReduceDefaultBlocks(int coll, uint64_t bytes) { return mscclpp_amd::pullReduceDefaultBlocks(coll, bytes); }
 
 }  // extern "C"

@@ -1,0 +1,264 @@
+// ncclMax / ncclAvg for Reduce, ReduceScatter and AllReduce: one zero-copy pull-reduce kernel.
+//
+// The reference carries SUM and MIN (and leaves the other operations to the vendor library), so
+// this is no restatement; the arithmetic is defined in mscclpp_amd/pull_reduce_device.hpp.  As in
+// reduce.hip every load of a peer's memory is a system-scope 16-byte buffer load of its user
+// buffer in place, the reduction happens in registers, and every store is a plain store into the
+// rank's own receive buffer: nothing is written to any peer.
+//
+//  * Geometry: a host-computed table.  Rank q reduces [srcOff[q], srcOff[q] + len[q]) of EVERY
+//    rank's send buffer, in rank order 0 .. n - 1, and stores the result at dstOff[q] of its own
+//    receive buffer.  Reduce: only the root's len is non-zero; ReduceScatter: srcOff[q] = q * bytes;
+//    AllReduce: q's slice of the message, and `gather` is set.  One `blk` (bytes per workgroup, a
+//    multiple of 16) comes from the largest len, so workgroup b owns the same sub-range b of every
+//    rank's range, and hand-shakes with the peers' workgroup b on channel b only.
+//  * Entry handshake (every workgroup, also one whose share is empty): all send buffers are final
+//    and every rank's earlier stream work on its receive buffer is over.
+//  * Phase 1: per 16-byte unit the own unit by a local load and the same unit of every peer's send
+//    buffer by load16<kSystem>, each at its position in rank order; the loads of all U units of a
+//    lane are issued before any arithmetic.  A lane stores only units it has itself loaded, and a
+//    rank's peers read from its send buffer only THEIR ranges, so the in-place forms hold: Reduce
+//    with send == recv on the root, ReduceScatter with recv == send + rank * bytes, AllReduce with
+//    send == recv.
+//  * AllReduce only: a middle handshake, then for every q != rank sub-range b of q's slice is
+//    copied out of peerOutput[q] (load16<kSystem>) into the own receive buffer.  Visibility is
+//    allreduceTestK5Kernel's discipline (allreduce_bulk.hip): phase 1 stores plainly, every wave
+//    drains its stores (s_waitcnt vmcnt(0)) and meets the workgroup barrier inside block_handshake,
+//    whose signalling lanes then run a system-scope release fence (the XCD's L2 written back, and
+//    waited for) before the token add; the peer reads with system-scope loads after its acquire.
+//    Write-through (sc0 sc1) stores would drop the lines from the L2 that the same rank's next
+//    kernel reads the result from, for no gain: the release is paid by the handshake anyway.
+//  * Exit handshake: every reader is done with this rank's send and receive buffers.
+//  * Tails and alignment as reduce.hip: the last unit of a range that is no multiple of 16 bytes
+//    moves byte by byte; no byte outside [recv + dstOff, + len) is written and none outside a send
+//    buffer's extent is read.  Pointers need their element's alignment only and the misalignment
+//    may differ between ranks and between send and receive: one descriptor per buffer, rebased to
+//    the workgroup's range (64-bit), with 32-bit offsets inside it.
+#include "common.hpp"
+#include "handshake.hpp"
+#include "mscclpp_amd/pull_reduce_device.hpp"
+
+namespace mscclpp_amd {
+
+// Units per lane in flight, from the resource report of the 32 instantiations (hipcc
+// -Rpass-analysis=kernel-resource-usage; DESIGN.md §17d has the table; none uses scratch).  As for
+// reduceKernel, U = 2 keeps 256 bytes of loads per lane in flight at 8 ranks and stays at or below
+// 128 VGPRs, i.e. two 512-lane workgroups per CU, which the in-process launch of 8 ranks x 64
+// workgroups needs to be resident at once.
+constexpr int kPullReduceUnits = 2;
+
+// ceil(len / nblocks) rounded up to whole 16-byte units, of the largest range of the collective.
+__host__ __device__ inline uint64_t pullReduceBlockBytes(uint64_t maxLen, uint32_t nblocks) {
+  return ((maxLen + nblocks - 1) / nblocks + 15) & ~15ull;
+}
+
+template <int NV>
+struct PullReduceArgs {
+  Views<NV> views;
+  uint64_t srcOff[kMaxRanks];  // rank q reduces [srcOff[q], + len[q]) of every send buffer
+  uint64_t dstOff[kMaxRanks];  // into its receive buffer at dstOff[q]
+  uint64_t len[kMaxRanks];
+  uint64_t blk;     // pullReduceBlockBytes(max len, gridDim.x)
+  uint64_t budget;
+  uint64_t* trace;  // phase stamps: 0 start, 1 entry handshake done, 2 reduced, 3 gathered, 4 end
+  float invN;       // 1.0f / (float)nranks, computed once by the host (AVG of the float types)
+  int nranks;
+  int gather;       // AllReduce: phase 2 copies the peers' reduced slices
+};
+static_assert(sizeof(PullReduceArgs<kMaxRanks>) <= 4096, "in-process pull-reduce arguments exceed the kernel-argument limit");
+
+template <int DT, int OP, int NV, int U>
+__global__ void __launch_bounds__(512) pullReduceKernel(PullReduceArgs<NV> a) {
+  const mscclppAmdRankView& v = a.views.v[NV == 1 ? 0 : blockIdx.y];
+  const int rank = v.rank, n = a.nranks;
+  const uint32_t T = blockDim.x, tid = threadIdx.x, b = blockIdx.x;
+  trace_stamp(a.trace, 0);
+  block_handshake(v, n, rank, b, a.budget);
+  trace_stamp(a.trace, 1);
+  const uint64_t bOff = (uint64_t)b * a.blk;
+  if (bOff < a.len[rank]) {
+    const uint64_t left = a.len[rank] - bOff;
+    const uint64_t len = left < a.blk ? left : a.blk;  // <= kBlkOffsetLimit
+    const uint32_t nUnits = (uint32_t)((len + 15) / 16);
+    const uint64_t sOff = a.srcOff[rank] + bOff;
+    const uint8_t* own = (const uint8_t*)v.input + sOff;
+    uint8_t* dst = (uint8_t*)v.output + a.dstOff[rank] + bOff;
+    const auto rin = make_rsrc(own);
+    const auto rout = make_rsrc(dst);
+    const uint8_t* pin[kMaxRanks];  // pin[k]: rank k's send buffer, this range
+#pragma unroll
+    for (int k = 0; k < kMaxRanks; ++k) pin[k] = k < n && k != rank ? (const uint8_t*)v.peerInput[k] + sOff : nullptr;
+    for (uint32_t u0 = tid; u0 < nUnits; u0 += T * U) {
+      u32x4 w[U][kMaxRanks];
+      uint32_t vb[U];
+#pragma unroll
+      for (int i = 0; i < U; ++i) {
+        const uint32_t u = u0 + i * T;
+        vb[i] = u < nUnits ? clamp_valid(len, (uint64_t)u * 16, 16) : 0;
+        if (vb[i] == 0) continue;
+#pragma unroll
+        for (int k = 0; k < kMaxRanks; ++k)
+          if (k < n) {
+            if (k == rank)
+              w[i][k] = load_payload<kNonTemporal>(rin, own, (uint64_t)u * 16, vb[i]);
+            else
+              w[i][k] = vb[i] >= 16 ? load16<kSystem>(make_rsrc(pin[k]), u * 16u) : load_tail(pin[k] + (uint64_t)u * 16, vb[i]);
+          }
+      }
+#pragma unroll
+      for (int i = 0; i < U; ++i) {
+        if (vb[i] == 0) continue;
+        const uint32_t u = u0 + i * T;
+        u32x4 r;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          PullAcc<DT, OP> acc;
+          acc.first(w[i][0][j]);
+#pragma unroll
+          for (int k = 1; k < kMaxRanks; ++k)
+            if (k < n) acc.next(w[i][k][j]);
+          r[j] = acc.word(n, a.invN);
+        }
+        store_payload<kPlain>(rout, dst, (uint64_t)u * 16, r, vb[i]);
+      }
+    }
+  }
+  trace_stamp(a.trace, 2);
+  if (a.gather) {
+    block_handshake(v, n, rank, b, a.budget);  // every peer's sub-range b of its slice is reduced and released
+#pragma unroll 1
+    for (int k = 1; k < n; ++k) {
+      const int q = (rank + k) % n;
+      if (bOff >= a.len[q]) continue;
+      const uint64_t left = a.len[q] - bOff;
+      const uint64_t len = left < a.blk ? left : a.blk;
+      const uint32_t nUnits = (uint32_t)((len + 15) / 16);
+      const uint64_t off = a.dstOff[q] + bOff;
+      const uint8_t* src = (const uint8_t*)v.peerOutput[q] + off;
+      uint8_t* dst = (uint8_t*)v.output + off;
+      const auto rs = make_rsrc(src);
+      const auto rd = make_rsrc(dst);
+      for (uint32_t u0 = tid; u0 < nUnits; u0 += T * U) {
+        u32x4 w[U];
+        uint32_t vb[U];
+#pragma unroll
+        for (int i = 0; i < U; ++i) {
+          const uint32_t u = u0 + i * T;
+          vb[i] = u < nUnits ? clamp_valid(len, (uint64_t)u * 16, 16) : 0;
+          if (vb[i]) w[i] = load_payload<kSystem>(rs, src, (uint64_t)u * 16, vb[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < U; ++i)
+          if (vb[i]) store_payload<kPlain>(rd, dst, (uint64_t)(u0 + i * T) * 16, w[i], vb[i]);
+      }
+    }
+    trace_stamp(a.trace, 3);
+  }
+  block_handshake(v, n, rank, b, a.budget);
+  trace_stamp(a.trace, 4);
+}
+
+static constexpr uint64_t kPullBlkOffsetLimit = 0xFFFFFFFFull - 64;  // as reduce.hip: one descriptor per workgroup range
+
+int reduceDefaultBlocks(uint64_t bytes);  // reduce.hip
+
+// The default grid is a function of (collective, bytes) alone, so every rank derives the same one;
+// the rules are read off the in-process sweep of DESIGN.md §17d (8 ranks on one GPU, 512 lanes).
+// Reduce: reduceDefaultBlocks (32 KiB of the message per workgroup, 8..64): only the root's workgroups
+// move data, and 8 / 32 / 64 are the fastest grids at 64 KiB / 1 MiB / 48 MiB here as there.
+// ReduceScatter (bytes = a rank's block): 32 KiB per workgroup, 8..32; AllReduce: 64 KiB of the message
+// per workgroup, 8..32.  In both every rank's workgroups move data, and 32 beat 64 at 48 MiB per rank
+// (8 ranks x 32 = one workgroup per CU of the one GPU measured; a rank alone on its GPU may want
+// more, which nobody has measured).  No rule exceeds 64, so that 8 in-process ranks x the default
+// grid of 512-lane workgroups (two per CU at this kernel's register count) are resident at once.
+int pullReduceDefaultBlocks(int coll, uint64_t bytes) {
+  if (coll == MSCCLPP_AMD_PULL_REDUCE) return reduceDefaultBlocks(bytes);
+  const uint64_t per = coll == MSCCLPP_AMD_PULL_ALLREDUCE ? (64u << 10) : (32u << 10);
+  const uint64_t want = (bytes + per - 1) / per;
+  return (int)(want < 8 ? 8 : want > 32 ? 32 : want);
+}
+
+// The one statement of the geometry (bytes: the message of Reduce / AllReduce, the per-rank block
+// of ReduceScatter).  Returns the largest len.
+uint64_t pullReduceGeometry(int coll, int nranks, uint64_t bytes, int root, uint64_t* srcOff, uint64_t* dstOff,
+                            uint64_t* len) {
+  uint64_t most = 0;
+  const uint64_t slice = ((bytes + (uint64_t)nranks - 1) / (uint64_t)nranks + 15) & ~15ull;
+  for (int q = 0; q < kMaxRanks; ++q) {
+    srcOff[q] = dstOff[q] = len[q] = 0;
+    if (q >= nranks) continue;
+    if (coll == MSCCLPP_AMD_PULL_REDUCE) {
+      len[q] = q == root ? bytes : 0;
+    } else if (coll == MSCCLPP_AMD_PULL_REDUCE_SCATTER) {
+      srcOff[q] = (uint64_t)q * bytes;
+      len[q] = bytes;
+    } else {
+      const uint64_t at = (uint64_t)q * slice;
+      srcOff[q] = dstOff[q] = at < bytes ? at : 0;
+      len[q] = at < bytes ? (bytes - at < slice ? bytes - at : slice) : 0;
+    }
+    most = len[q] > most ? len[q] : most;
+  }
+  return most;
+}
+
+static thread_local int g_pull_reduce_status = 0;
+
+template <int DT, int OP>
+static void launchPullReduceT(const mscclppAmdRankView* views, int nviews, int nranks, int coll, uint64_t bytes, int root,
+                              uint64_t blk, int nblocks, int nthreads, uint64_t budget, hipStream_t s) {
+  auto go = [&](auto kern, auto args) {
+    for (int i = 0; i < nviews; ++i) args.views.v[i] = views[i];
+    pullReduceGeometry(coll, nranks, bytes, root, args.srcOff, args.dstOff, args.len);
+    args.blk = blk;
+    args.budget = budget;
+    args.trace = g_mscclppAmdTrace;
+    args.invN = 1.0f / (float)nranks;
+    args.nranks = nranks;
+    args.gather = coll == MSCCLPP_AMD_PULL_ALLREDUCE;
+    if (!grid_coresident(kern, nthreads, (long)nblocks * nviews)) {
+      g_pull_reduce_status = 5;  // ncclInvalidUsage: the handshakes of a non-resident grid would deadlock
+      return;
+    }
+    hipLaunchKernelGGL(kern, dim3(nblocks, nviews), dim3(nthreads), 0, s, args);
+  };
+  if (nviews == 1)
+    go(pullReduceKernel<DT, OP, 1, kPullReduceUnits>, PullReduceArgs<1>{});
+  else
+    go(pullReduceKernel<DT, OP, kMaxRanks, kPullReduceUnits>, PullReduceArgs<kMaxRanks>{});
+}
+
+#define MSCCLPP_AMD_PULL_CASE2(DT, ...)                                            \
+  case DT * 4 + kPullMax: launchPullReduceT<DT, kPullMax>(__VA_ARGS__); break;     \
+  case DT * 4 + kPullAvg: launchPullReduceT<DT, kPullAvg>(__VA_ARGS__); break;
+
+int launchPullReduce(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes, int dtype, int op,
+                     int root, int nblocks, int nthreads, uint64_t budget, hipStream_t s) {
+  if (coll < MSCCLPP_AMD_PULL_REDUCE || coll > MSCCLPP_AMD_PULL_ALLREDUCE) return 4;
+  if (nblocks <= 0) nblocks = pullReduceDefaultBlocks(coll, bytes);
+  if (nthreads <= 0) nthreads = 512;
+  if (nblocks > kMaxChannels || nthreads > 512 || nthreads % 64 || nthreads < 64) return 4;
+  if (nranks < 2 || nranks > kMaxRanks || bytes == 0) return 4;
+  if (coll == MSCCLPP_AMD_PULL_REDUCE && (root < 0 || root >= nranks)) return 4;
+  if ((op != kPullMax && op != kPullAvg) || !pull_reduce_carries(dtype) || bytes % (size_t)elem_bytes(dtype)) return 4;
+  uint64_t srcOff[kMaxRanks], dstOff[kMaxRanks], len[kMaxRanks];
+  const uint64_t most = pullReduceGeometry(coll, nranks, bytes, root, srcOff, dstOff, len);
+  const uint64_t blk = pullReduceBlockBytes(most, (uint32_t)nblocks);
+  if (blk > kPullBlkOffsetLimit) return 5;  // more workgroups needed: one workgroup's range is one descriptor
+  g_pull_reduce_status = 0;
+  switch (dtype * 4 + op) {
+    MSCCLPP_AMD_PULL_CASE2(kF16, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)
+    MSCCLPP_AMD_PULL_CASE2(kBF16, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)
+    MSCCLPP_AMD_PULL_CASE2(kF32, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)
+    MSCCLPP_AMD_PULL_CASE2(kI32, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)
+    MSCCLPP_AMD_PULL_CASE2(kU32, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)
+    MSCCLPP_AMD_PULL_CASE2(kE4M3, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)
+    MSCCLPP_AMD_PULL_CASE2(kE5M2, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)
+    MSCCLPP_AMD_PULL_CASE2(kU8, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)
+    default: return 4;
+  }
+  if (g_pull_reduce_status) return g_pull_reduce_status;
+  return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+}  // namespace mscclpp_amd

@@ -1,0 +1,173 @@
+"""Fabric-free timing of the ncclMax / ncclAvg kernel (kernels/pull_reduce.hip): 8 ranks in ONE launch
+on one GPU (blockIdx.y = rank, every peer buffer local HBM), so no link is priced -- what is measured
+is the memory pipeline and the handshakes (two; three for an AllReduce).  Per dtype (fp16, bf16) and
+size S (bytes of a rank's send buffer; a ReduceScatter's block is S / n), each timing from a HIP
+graph of K calls, median of ROUNDS with the spread:
+
+  sweep      AVG AllReduce / ReduceScatter / Reduce at nblocks in {8, 16, 32, 64} x 512 lanes (fp16): the
+             default-grid rule (pullReduceDefaultBlocks) is read off this
+  lines      at the default shapes, alternating in the same run: AVG AllReduce / ReduceScatter / Reduce
+             and the SUM paths at the same shapes -- rsag_zc AllReduce, the selector's ReduceScatter
+             (tuned-config store; fullmesh 8 x 256 where it names none), reduceKernel
+  latency    MAX AllReduce (fp32) of 4 bytes and 1 KiB beside the LL8 (allpair) SUM AllReduce
+
+An AllReduce here moves the bytes of rsag_zc over the links, 2 (n - 1) / n * S per rank, all of them as
+reads (rsag_zc: half reads, half remote stores); whether reads beat remote stores over real xGMI
+links this tool cannot say.
+
+    python tools/pull_reduce_perf.py   (writes profiles/pull_reduce_perf_inprocess_n8.json, or $OUT)
+"""
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import mscclpp_amd as m  # noqa: E402
+
+N = int(os.environ.get("NRANKS", 8))
+SIZES = [int(s) for s in os.environ.get("SIZES", f"{48 << 20},{1 << 20},{64 << 10}").split(",")]
+ROUNDS = int(os.environ.get("ROUNDS", 5))
+ROOT_RANK = int(os.environ.get("ROOT_RANK", 3)) % N
+SWEEP_BLOCKS = (8, 16, 32, 64)
+COLLS = (("allreduce", m.PULL_ALLREDUCE), ("reducescatter", m.PULL_REDUCE_SCATTER), ("reduce", m.PULL_REDUCE))
+BUDGET = 300_000_000
+dev = torch.device("cuda", 0)
+torch.cuda.set_device(dev)
+
+
+def graph_us(fn, calls, replays):
+    """us per call of fn, from `replays` replays of a graph of `calls` calls (events around them)."""
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        fn()  # eager once on this stream: first-launch set-up stays out of the capture
+    s.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        for _ in range(calls):
+            fn()
+    g.replay()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(replays):
+        g.replay()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / (calls * replays)
+
+
+def stat(v):
+    return {"us": round(float(np.median(v)), 2), "us_min_max": [round(min(v), 2), round(max(v), 2)]}
+
+
+def cur():
+    return torch.cuda.current_stream()
+
+
+rows = []
+for tdt in (torch.float16, torch.bfloat16):
+    for S in SIZES:
+        count, blk = S // 2, S // 2 // N
+        sends = [torch.rand(count, dtype=torch.float32, device=dev).to(tdt) for _ in range(N)]
+        full = [torch.zeros(count, dtype=tdt, device=dev) for _ in range(N)]
+        part = [torch.zeros(blk, dtype=tdt, device=dev) for _ in range(N)]
+        outs = {m.PULL_ALLREDUCE: full, m.PULL_REDUCE_SCATTER: part,
+                m.PULL_REDUCE: [full[r] if r == ROOT_RANK else None for r in range(N)]}
+        ins = {c: ([t[:blk * N] for t in sends] if c == m.PULL_REDUCE_SCATTER else sends) for _, c in COLLS}
+        rs_cfg = m.tuned_config("reducescatter", N, blk * N * 2)
+        rs_algo = m.ALGO_NAMES.get((rs_cfg[0] if rs_cfg else "").replace("default_reducescatter_", ""), 0)
+        if rs_algo not in (m.ALGO_FULLMESH, m.ALGO_RSAG):
+            rs_algo, rs_cfg = m.ALGO_FULLMESH, None
+        bulk = max(m.scratch_required(rs_algo, N, blk * N * 2, m.reduce_code(tdt)), 1 << 20)
+        ranks = m.InProcessRanks(N, 1 << 16, bulk_scratch_bytes=bulk)
+
+        def avg(coll, nblocks=0):
+            ranks.pull_reduce(coll, ins[coll], outs[coll], m.AVG, root=ROOT_RANK, nblocks=nblocks, budget_ticks=BUDGET,
+                              stream=cur())
+
+        def sum_allreduce():
+            ranks.all_reduce(sends, full, m.ALGO_RSAG_ZC, budget_ticks=BUDGET, stream=cur())
+
+        def sum_reducescatter():
+            shape = {"nblocks": rs_cfg[1], "nthreads": rs_cfg[2]} if rs_cfg and rs_cfg[1] > 0 else {}
+            ranks.collective(1, ins[m.PULL_REDUCE_SCATTER], part, algo=rs_algo, budget_ticks=BUDGET, stream=cur(), **shape)
+
+        def sum_reduce():
+            ranks.reduce(sends, outs[m.PULL_REDUCE], ROOT_RANK, budget_ticks=BUDGET, stream=cur())
+
+        # correctness of what is timed: the mean in fp32, rank order, rounded once (values in [0, 1))
+        want = sends[0].float()
+        for k in range(1, N):
+            want = want + sends[k].float()
+        want = (want * (np.float32(1.0) / np.float32(N))).to(tdt)
+        ok = True
+        for _, c in COLLS:
+            avg(c)
+        torch.cuda.synchronize()
+        ok = ok and all(torch.equal(t, want) for t in full)
+        ok = ok and all(torch.equal(part[r], want[r * blk:(r + 1) * blk]) for r in range(N))
+        ok = ok and ranks.errors() == [0] * N
+        calls, replays = (10, 5) if S >= (8 << 20) else (50, 10)
+        row = {"dtype": str(tdt).replace("torch.", ""), "send_bytes_per_rank": S, "root": ROOT_RANK, "correct": bool(ok),
+               "graph_calls": calls, "replays": replays, "rounds": ROUNDS,
+               "default_nblocks": {name: m.lib().mscclppAmdPullReduceDefaultBlocks(c, blk * 2 if c == m.PULL_REDUCE_SCATTER else S)
+                                   for name, c in COLLS},
+               "sum_reducescatter_algo": rs_cfg[0] if rs_cfg else "fullmesh (8 x 256)"}
+        if tdt == torch.float16:
+            sweep = {}
+            for name, c in COLLS:
+                sweep[name] = []
+                for nblocks in SWEEP_BLOCKS:
+                    t = [graph_us(lambda: avg(c, nblocks), calls, replays) for _ in range(ROUNDS)]
+                    sweep[name].append(dict(nblocks=nblocks, nthreads=512, **stat(t)))
+            row["sweep"] = sweep
+        lines = [("avg_" + name, (lambda c=c: avg(c))) for name, c in COLLS]
+        lines += [("sum_allreduce_rsag_zc", sum_allreduce), ("sum_reducescatter", sum_reducescatter),
+                  ("sum_reduce", sum_reduce)]
+        t = {name: [] for name, _ in lines}
+        for _ in range(ROUNDS):
+            for name, fn in lines:
+                t[name].append(graph_us(fn, calls, replays))
+        row["lines"] = {name: stat(v) for name, v in t.items()}
+        row["errors"] = ranks.errors()
+        if S == max(SIZES) and tdt == torch.float16:
+            with m.PhaseTrace() as tr:
+                avg(m.PULL_ALLREDUCE)
+                torch.cuda.synchronize()
+            row["phases_allreduce"] = tr.phases("pull_allreduce", view=ROOT_RANK)
+        rows.append(row)
+        print(row, flush=True)
+        del sends, full, part, outs, ins, ranks
+
+# small-message latency: MAX AllReduce (three handshakes) beside LL8 (allpair, SUM)
+latency = []
+for nbytes in (4, 1024):
+    count = nbytes // 4
+    x = [torch.rand(count, dtype=torch.float32, device=dev) for _ in range(N)]
+    y = [torch.zeros(count, dtype=torch.float32, device=dev) for _ in range(N)]
+    ranks = m.InProcessRanks(N, max(m.scratch_required(m.ALGO_ALLPAIR, N, nbytes, m.F32), 1 << 16))
+    fns = {"max_allreduce_default_grid": lambda: ranks.pull_reduce(m.PULL_ALLREDUCE, x, y, m.MAX, budget_ticks=BUDGET, stream=cur()),
+           "max_allreduce_1_workgroup": lambda: ranks.pull_reduce(m.PULL_ALLREDUCE, x, y, m.MAX, nblocks=1, nthreads=64,
+                                                                  budget_ticks=BUDGET, stream=cur()),
+           "sum_allreduce_ll8": lambda: ranks.all_reduce(x, y, m.ALGO_ALLPAIR, budget_ticks=BUDGET, stream=cur())}
+    t = {k: [] for k in fns}
+    for _ in range(ROUNDS):
+        for k, fn in fns.items():
+            t[k].append(graph_us(fn, 50, 10))
+    fns["max_allreduce_default_grid"]()
+    torch.cuda.synchronize()
+    ok = all(torch.equal(v, torch.stack(x).max(dim=0).values) for v in y) and ranks.errors() == [0] * N
+    latency.append(dict(bytes=nbytes, dtype="float32", correct=bool(ok), **{k: stat(v) for k, v in t.items()}))
+    print(latency[-1], flush=True)
+    del ranks
+
+res = {"tool": "tools/pull_reduce_perf.py", "fabric_free": True, "gpus": 1, "nranks": N,
+       "note": "in-process ranks on one GPU: no xGMI byte is priced; graph-captured, median of rounds",
+       "rows": rows, "latency": latency}
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+out = os.environ.get("OUT", os.path.join(ROOT, "profiles", f"pull_reduce_perf_inprocess_n{N}.json"))
+os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+json.dump(res, open(out, "w"), indent=1)
