@@ -309,6 +309,9 @@ std::shared_ptr<Algorithm> defaultAlgoSelector(const AlgoMapByCollective& algoMa
   int nb = 0, nt = 0;
   if (tunedConfig(request.collective, request.worldSize, request.messageSize, name, nb, nt))
     if (auto a = lookup(algoMap, request.collective, name.c_str())) return a;
+  // Fallbacks for a store without an entry.  Not reached for these three collectives: the built-in
+  // table of tuning.cpp has a size-1 entry for each, so the lookup above answers every size, and the
+  // live thresholds are that table's message_size values (16385, 1048577), not the literals below.
   if (request.collective == "allreduce") {
     const char* def = request.messageSize <= ((size_t)1 << 14)   ? "default_allreduce_allpair_packet"
                       : request.messageSize <= ((size_t)1 << 20) ? "default_allreduce_packet"

@@ -191,6 +191,9 @@ int mscclppAmdSelectAlgo(int nranks, size_t bytes, int dtype) {
     }
   } catch (...) {
   }
+  // Fallback for a store without an allreduce entry or with a name this library does not know (a
+  // loaded profile may name one).  With the built-in table alone it is not reached: that table
+  // answers every size, and its message_size values are the live thresholds.
   if (bytes <= ((size_t)1 << 14)) return MSCCLPP_AMD_ALGO_ALLPAIR;
   if (bytes <= ((size_t)1 << 20)) return MSCCLPP_AMD_ALGO_PACKET;
   return MSCCLPP_AMD_ALGO_FULLMESH;
@@ -468,13 +471,14 @@ ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, n
     const int o = opFromNccl(op), po = pullOpFromNccl(op);
     if (comm->fallback && (dt < 0 || (o < 0 && po < 0) || forcedFallback("allreduce")))  // nccl.cc:628-632
       return (int)vendorNccl()->AllReduce(sendbuff, recvbuff, count, datatype, op, (ncclComm_t)comm->fallback, stream);
-    if (dt >= 0 && po >= 0) {  // ncclMax / ncclAvg: the pull-reduce kernel (no Algorithm: no selector is asked)
-      if (sendbuff != recvbuff && bufferRangesOverlap(sendbuff, bytes, recvbuff, bytes)) {
-        warn("ncclAllReduce: the send and receive ranges overlap without being identical");
-        return (int)ncclInvalidArgument;
-      }
-      return comm->pullReduce(MSCCLPP_AMD_PULL_ALLREDUCE, sendbuff, recvbuff, bytes, dt, po, 0, (hipStream_t)stream);
+    // every native path reads the send range (its own and, zero-copy, the peers') while receive ranges
+    // are written: only the identical range (in place) may overlap
+    if (sendbuff != recvbuff && bufferRangesOverlap(sendbuff, bytes, recvbuff, bytes)) {
+      warn("ncclAllReduce: the send and receive ranges overlap without being identical");
+      return (int)ncclInvalidArgument;
     }
+    if (dt >= 0 && po >= 0)  // ncclMax / ncclAvg: the pull-reduce kernel (no Algorithm: no selector is asked)
+      return comm->pullReduce(MSCCLPP_AMD_PULL_ALLREDUCE, sendbuff, recvbuff, bytes, dt, po, 0, (hipStream_t)stream);
     if (dt < 0 || o < 0) {
       warn("unsupported dtype/op for AllReduce (supported: fp16, bf16, fp32, int32, uint32, uint8, fp8 e4m3/e5m2 x sum, "
            "min, max, avg)");
@@ -500,16 +504,15 @@ ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recv
     if (comm->fallback && (dt < 0 || (o < 0 && po < 0) || forcedFallback("reducescatter")))  // nccl.cc:682-686
       return (int)vendorNccl()->ReduceScatter(sendbuff, recvbuff, recvcount, datatype, op, (ncclComm_t)comm->fallback,
                                               stream);
-    if (dt >= 0 && po >= 0) {  // ncclMax / ncclAvg: the pull-reduce kernel (no Algorithm: no selector is asked)
-      // in place is recv == send + rank * bytes: a lane stores only units it has loaded, and the
-      // peers read other blocks of the send buffer
-      const char* mine = (const char*)sendbuff + (size_t)comm->rank * bytes;
-      if (recvbuff != mine && bufferRangesOverlap(sendbuff, bytes * (size_t)comm->nranks, recvbuff, bytes)) {
-        warn("ncclReduceScatter: the receive range overlaps the send buffer elsewhere than at its own block");
-        return (int)ncclInvalidArgument;
-      }
-      return comm->pullReduce(MSCCLPP_AMD_PULL_REDUCE_SCATTER, sendbuff, recvbuff, bytes, dt, po, 0, (hipStream_t)stream);
+    // in place is recv == send + rank * bytes: a lane stores only units it has loaded, and the
+    // peers read other blocks of the send buffer.  Any other overlap is refused on every native path.
+    const char* mine = (const char*)sendbuff + (size_t)comm->rank * bytes;
+    if (recvbuff != mine && bufferRangesOverlap(sendbuff, bytes * (size_t)comm->nranks, recvbuff, bytes)) {
+      warn("ncclReduceScatter: the receive range overlaps the send buffer elsewhere than at its own block");
+      return (int)ncclInvalidArgument;
     }
+    if (dt >= 0 && po >= 0)  // ncclMax / ncclAvg: the pull-reduce kernel (no Algorithm: no selector is asked)
+      return comm->pullReduce(MSCCLPP_AMD_PULL_REDUCE_SCATTER, sendbuff, recvbuff, bytes, dt, po, 0, (hipStream_t)stream);
     if (dt < 0 || o < 0) return (int)ncclInvalidArgument;
     const size_t total = bytes * (size_t)comm->nranks;  // messageSize = bytes * nRank (nccl.cc:692-697)
     return selectAndExecute(comm, "reducescatter", sendbuff, recvbuff, total, total, bytes, datatype, op, stream);

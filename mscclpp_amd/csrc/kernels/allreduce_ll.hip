@@ -245,8 +245,15 @@ constexpr uint32_t kBatchedPollUnits = 8192;
 // round trip costs 0.2 us (1-256 KiB) more than the re-reads it saves
 // (tools/ll_variants_ab.py, profiles/r3d_ll_sentinel_ab.json).
 constexpr uint32_t kSentinelUnits = 8192;
+// Two 512-lane workgroups per CU (4 waves per SIMD: at most 128 VGPRs).  Left to itself the compiler
+// took 222-225 VGPRs for bf16, fp32 and fp16 MIN (fp16 SUM: 85), one workgroup per CU, so the default
+// grids of eight ranks sharing one GPU (8 x 56 workgroups from 256 KiB) were not resident together
+// and every rank's waits ran into the spin budget.  With the bound all types take 83-100, no spill.
+// Ranks share a GPU only in the tests.  With one rank per GPU the bound changes the code the compiler
+// emits for those variants (fp16 SUM is unchanged at 84-85); its LL16 times have not been measured
+// per size and type since.
 template <int DT, int OP, int NV, int V = 0>
-__global__ void __launch_bounds__(512) allreduceLL16Kernel(Views<NV> views, LL16Geom g, int nranks, uint64_t budget) {
+__global__ void __launch_bounds__(512, 4) allreduceLL16Kernel(Views<NV> views, LL16Geom g, int nranks, uint64_t budget) {
   const mscclppAmdRankView& v = views.v[NV == 1 ? 0 : blockIdx.y];
   const int rank = v.rank;
   const int nPeers = nranks - 1;

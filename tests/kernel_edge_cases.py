@@ -97,6 +97,26 @@ def expected(algo, dt, op, ins, count, flag=1, half_bytes=1 << 20):
     return [o.view(np.uint8)[:nbytes] for o in outs], scr
 
 
+def pipeline_expected(dt, op, ins, nbytes, n, R, T):
+    """Oracle for allreduceRsAgPipeline (allreduce_rsag_pipeline.cu:85-222): 16-byte unit u is owned
+    by slot (u mod n*C) div C (C = R*T*4 units) and summed in ring order from its owner (own,
+    owner+1, ...; calVector(data, tmp) with tmp = own first)."""
+    nw = (nbytes + 15) // 16 * 4
+    padded = []
+    for a in ins:
+        w = np.zeros(nw, np.uint32)
+        w.view(np.uint8)[:nbytes] = a.view(np.uint8)[:nbytes]
+        padded.append(w)
+    C = R * T * 4
+    owner = ((np.arange(nw) // 4) % (n * C)) // C
+    exp = np.zeros(nw, np.uint32)
+    for o in range(n):
+        order = [padded[(o + k) % n] for k in range(n)]
+        seq = O.reduce_seq(dt, op, order)
+        exp[owner == o] = seq[owner == o]
+    return exp
+
+
 # ---- A: launch shapes ----------------------------------------------------------------------------
 def _ll16_shapes(n):
     p = n - 1

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_edge_cases as K
 import oracle_lib as O
 
 pytestmark = pytest.mark.gpu
@@ -252,24 +253,7 @@ def test_tiny_buffers(built, algo, dt, count, op):
             _cmp(_bytes(douts[r]), exp.view(np.uint8)[:nbytes], dt)
 
 
-def _pipeline_expected(dt, op, ins, nbytes, n, R, T):
-    """Oracle for allreduceRsAgPipeline (allreduce_rsag_pipeline.cu:85-222): 16-byte unit u is owned
-    by slot (u mod n*C) div C (C = R*T*4 units) and summed in ring order from its owner (own,
-    owner+1, ...; calVector(data, tmp) with tmp = own first)."""
-    nw = (nbytes + 15) // 16 * 4
-    padded = []
-    for a in ins:
-        w = np.zeros(nw, np.uint32)
-        w.view(np.uint8)[:nbytes] = a.view(np.uint8)[:nbytes]
-        padded.append(w)
-    C = R * T * 4
-    owner = ((np.arange(nw) // 4) % (n * C)) // C
-    exp = np.zeros(nw, np.uint32)
-    for o in range(n):
-        order = [padded[(o + k) % n] for k in range(n)]
-        seq = O.reduce_seq(dt, op, order)
-        exp[owner == o] = seq[owner == o]
-    return exp
+_pipeline_expected = K.pipeline_expected  # shared with test_mixed_collectives_gpu.py
 
 
 @pytest.mark.parametrize("n,dt,count,R,T,stages", [
