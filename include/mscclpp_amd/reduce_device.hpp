@@ -355,26 +355,22 @@ __device__ __forceinline__ u32x4 reduce4(u32x4 a, u32x4 b) {
   }
 }
 
-// Runtime (dtype, op) -> template dispatch for kernels templated on <DT, OP>.
-#define MSCCLPP_AMD_DISPATCH(dtype, op, FN, ...)                 \
-  switch ((dtype) * 2 + (op)) {                                  \
-    case kF16 * 2 + kSum: FN<kF16, kSum>(__VA_ARGS__); break;    \
-    case kF16 * 2 + kMin: FN<kF16, kMin>(__VA_ARGS__); break;    \
-    case kBF16 * 2 + kSum: FN<kBF16, kSum>(__VA_ARGS__); break;  \
-    case kBF16 * 2 + kMin: FN<kBF16, kMin>(__VA_ARGS__); break;  \
-    case kF32 * 2 + kSum: FN<kF32, kSum>(__VA_ARGS__); break;    \
-    case kF32 * 2 + kMin: FN<kF32, kMin>(__VA_ARGS__); break;    \
-    case kI32 * 2 + kSum: FN<kI32, kSum>(__VA_ARGS__); break;    \
-    case kI32 * 2 + kMin: FN<kI32, kMin>(__VA_ARGS__); break;    \
-    case kU32 * 2 + kSum: FN<kU32, kSum>(__VA_ARGS__); break;    \
-    case kU32 * 2 + kMin: FN<kU32, kMin>(__VA_ARGS__); break;    \
-    default: return 4; /* invalid argument */                    \
-  }
-
-// Both ops of one reduce type.
+// Runtime (dtype, op) -> template dispatch for launchers templated on <DT, OP>: the enclosing
+// function returns FN<DT, OP>(args), or 4 (invalid argument) for a pair outside the set.
+// Both ops of one reduce type:
 #define MSCCLPP_AMD_CASE2(DT, FN, ...)                      \
-  case DT * 2 + kSum: FN<DT, kSum>(__VA_ARGS__); break;     \
-  case DT * 2 + kMin: FN<DT, kMin>(__VA_ARGS__); break;
+  case DT * 2 + kSum: return FN<DT, kSum>(__VA_ARGS__);     \
+  case DT * 2 + kMin: return FN<DT, kMin>(__VA_ARGS__);
+
+#define MSCCLPP_AMD_DISPATCH(dtype, op, FN, ...)         \
+  switch ((dtype) * 2 + (op)) {                          \
+    MSCCLPP_AMD_CASE2(kF16, FN, __VA_ARGS__)             \
+    MSCCLPP_AMD_CASE2(kBF16, FN, __VA_ARGS__)            \
+    MSCCLPP_AMD_CASE2(kF32, FN, __VA_ARGS__)             \
+    MSCCLPP_AMD_CASE2(kI32, FN, __VA_ARGS__)             \
+    MSCCLPP_AMD_CASE2(kU32, FN, __VA_ARGS__)             \
+    default: return 4;                                   \
+  }
 
 // As MSCCLPP_AMD_DISPATCH, plus the 1-byte reduce types: OCP FP8 and e4m3b15 with their
 // accumulation types (dispatchFp8Accum, common.hpp:89-100) and uint8.
@@ -395,7 +391,7 @@ __device__ __forceinline__ u32x4 reduce4(u32x4 a, u32x4 b) {
     MSCCLPP_AMD_CASE2(kB15, FN, __VA_ARGS__)             \
     MSCCLPP_AMD_CASE2(kB15AccF16, FN, __VA_ARGS__)       \
     MSCCLPP_AMD_CASE2(kB15AccF32, FN, __VA_ARGS__)       \
-    default: return 4; /* invalid argument */            \
+    default: return 4;                                   \
   }
 
 }  // namespace mscclpp_amd

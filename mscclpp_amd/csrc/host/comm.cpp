@@ -84,8 +84,7 @@ int mscclppAmdFlagsInit(uint32_t* flags, void* stream) {
 int mscclppAmdAllReduceLaunch(int algo, const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes,
                               int dtype, int op, int nblocks, int nthreads, uint64_t budgetTicks, void* stream) {
   return guarded([&] {
-    if (!views || nviews < 1 || nranks < 2 || nranks > MSCCLPP_AMD_MAX_RANKS || bytes == 0) return (int)ncclInvalidArgument;
-    if (nviews != 1 && nviews != nranks) return (int)ncclInvalidArgument;
+    if (bytes == 0) return (int)ncclInvalidArgument;
     if (dtype < 0 || dtype >= MSCCLPP_AMD_NUM_DTYPES || op < 0 || op > MSCCLPP_AMD_MIN) return (int)ncclInvalidArgument;
     if (algo == MSCCLPP_AMD_ALGO_AUTO) algo = mscclppAmdSelectAlgo(nranks, bytes, dtype);
     if (budgetTicks == 0) budgetTicks = spinBudgetTicks();
@@ -94,34 +93,28 @@ int mscclppAmdAllReduceLaunch(int algo, const mscclppAmdRankView* views, int nvi
     const bool k5 = algo == MSCCLPP_AMD_ALGO_TEST_K5;
     const bool zc = algo == MSCCLPP_AMD_ALGO_RSAG_ZC || k5;  // no scratch: peers' user buffers directly
     const bool bulk = algo == MSCCLPP_AMD_ALGO_FULLMESH || algo == MSCCLPP_AMD_ALGO_RSAG || zc;
+    ViewNeeds needs;
+    needs.all = kViewInput | kViewOutput | kViewErr;
     if (algo == MSCCLPP_AMD_ALGO_RSAG_PIPELINE) {
-      for (int i = 0; i < nviews; ++i) {
-        const mscclppAmdRankView& v = views[i];
-        if (!v.input || !v.output || !v.scratch || !v.pipeSems || !v.tokens || !v.expected || !v.err)
-          return (int)ncclInvalidArgument;
-        for (int q = 0; q < nranks; ++q)
-          if (!v.peerScratch[q] || !v.peerTokens[q]) return (int)ncclInvalidArgument;
-      }
+      needs.all |= kViewScratch | kViewPipeSems | kViewTokens | kViewPeerScratch;
+      needs.rank = false;
+      if (!viewsValid(views, nviews, nranks, needs)) return (int)ncclInvalidArgument;
       return launchAllReducePipeline(views, nviews, nranks, bytes, dtype, op, nblocks, nthreads, budgetTicks,
                                      (hipStream_t)stream);
     }
     const bool ll = algo == MSCCLPP_AMD_ALGO_PACKET || algo == MSCCLPP_AMD_ALGO_ALLPAIR ||
                     algo == MSCCLPP_AMD_ALGO_TEST_K6 || algo == MSCCLPP_AMD_ALGO_TEST_K7 ||
                     algo == MSCCLPP_AMD_ALGO_TEST_K2;
+    needs.all |= kViewFlags | (zc ? 0u : kViewScratch | kViewPeerScratch) | (bulk ? kViewTokens | kViewPeerOutput : 0u) |
+                 (zc && !k5 ? kViewPeerInput : 0u);
+    if (!viewsValid(views, nviews, nranks, needs)) return (int)ncclInvalidArgument;
     unsigned seen = 0;
     for (int i = 0; i < nviews; ++i) {
       const mscclppAmdRankView& v = views[i];
-      if (v.rank < 0 || v.rank >= nranks || (seen >> v.rank) & 1u) return (int)ncclInvalidArgument;
+      if ((seen >> v.rank) & 1u) return (int)ncclInvalidArgument;  // no rank twice
       seen |= 1u << v.rank;
-      if (!v.input || !v.output || !v.flags || !v.err) return (int)ncclInvalidArgument;
       if (ll && ((uintptr_t)v.flags % 16)) return (int)ncclInvalidArgument;  // 16-byte flag refresh
-      if (!zc && (!v.scratch || v.scratchBytes == 0)) return (int)ncclInvalidArgument;
-      for (int q = 0; q < nranks; ++q) {
-        if (!zc && !v.peerScratch[q]) return (int)ncclInvalidArgument;
-        if (bulk && (!v.peerOutput[q] || !v.peerTokens[q])) return (int)ncclInvalidArgument;
-        if (zc && !k5 && !v.peerInput[q]) return (int)ncclInvalidArgument;
-      }
-      if (bulk && (!v.tokens || !v.expected)) return (int)ncclInvalidArgument;
+      if (!zc && v.scratchBytes == 0) return (int)ncclInvalidArgument;
     }
     if (ll)
       return launchAllReduceLL(algo, views, nviews, nranks, bytes, dtype, op, nblocks, nthreads, budgetTicks,
@@ -140,15 +133,11 @@ int mscclppAmdCollectiveLaunch(int coll, int algo, const mscclppAmdRankView* vie
     return mscclppAmdAllReduceLaunch(algo, views, nviews, nranks, bytes, dtype, op, nblocks, nthreads, budgetTicks,
                                      stream);
   return guarded([&] {
-    if (!views || nviews < 1 || nranks < 2 || nranks > MSCCLPP_AMD_MAX_RANKS || bytes == 0) return (int)ncclInvalidArgument;
-    if (nviews != 1 && nviews != nranks) return (int)ncclInvalidArgument;
+    ViewNeeds needs;
+    needs.all = kViewInput | kViewOutput | kViewScratch | kViewHandshake | kViewPeerScratch | kViewPeerOutput;
+    needs.rank = false;
+    if (!viewsValid(views, nviews, nranks, needs) || bytes == 0) return (int)ncclInvalidArgument;
     if (coll != 1 && coll != 2) return (int)ncclInvalidArgument;
-    for (int i = 0; i < nviews; ++i) {
-      const mscclppAmdRankView& v = views[i];
-      if (!v.input || !v.output || !v.scratch || !v.tokens || !v.expected || !v.err) return (int)ncclInvalidArgument;
-      for (int q = 0; q < nranks; ++q)
-        if (!v.peerScratch[q] || !v.peerTokens[q] || !v.peerOutput[q]) return (int)ncclInvalidArgument;
-    }
     return launchCollectiveBulk(coll, algo, views, nviews, nranks, bytes, dtype, op, nblocks, nthreads,
                                 budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream);
   });

@@ -703,21 +703,29 @@ struct ncclComm {
   std::array<bool, MSCCLPP_AMD_MAX_RANKS> bcastCaptured{};  // bcastMaps[root] used under capture
   std::vector<std::shared_ptr<void>> bcastPinned;             // replaced, but a graph may read them
 
+  // The view of a zero-copy pull collective, for a launch that starts here: peerInput[q] is rank q's
+  // send buffer, registered through `send` (registerOutput, or registerPaired where the caller
+  // gathered every rank's sendIdent).  recordUses follows the launch.
+  struct SendIdent;
+  mscclppAmdRankView pullView(const void* send, void* recv, hipStream_t stream, const SendIdent* idents = nullptr) {
+    touched.clear();
+    mscclppAmdRankView v = baseView(send, recv);
+    const auto ins = idents ? registerPaired(const_cast<void*>(send), idents, stream)
+                            : registerOutput(const_cast<void*>(send), stream);
+    for (int r = 0; r < nranks; ++r) v.peerInput[r] = ins[r];
+    return v;
+  }
+
   // AllToAll(v) by a zero-copy pull (kernels/alltoall.hip): segs[p] = what this rank receives from
   // rank p, in bytes.  The send buffer is what the peers read, so it is the one registered
   // (collective on first use, cached per allocation, pinned under capture); every store goes to this
   // rank's own receive buffer, which needs no registration.  nblocks: the same on every rank.
   // idents: every rank's sendIdent of this call where the caller gathered them (AllToAllv,
   // registerPaired); null: registerOutput, the other collectives' contract of matching buffers.
-  struct SendIdent;
   int allToAll(const void* send, void* recv, const mscclppAmdAllToAllSeg* segs, int nblocks, hipStream_t stream,
                const SendIdent* idents = nullptr) {
     std::lock_guard<std::mutex> lk(mu);
-    touched.clear();
-    mscclppAmdRankView v = baseView(send, recv);
-    const auto ins = idents ? registerPaired(const_cast<void*>(send), idents, stream)
-                            : registerOutput(const_cast<void*>(send), stream);
-    for (int r = 0; r < nranks; ++r) v.peerInput[r] = ins[r];
+    mscclppAmdRankView v = pullView(send, recv, stream, idents);
     const int rc = launchAllToAll(&v, 1, nranks, segs, nblocks, 0, spinBudgetTicks(), stream);
     recordUses(stream);
     return rc;
@@ -730,10 +738,7 @@ struct ncclComm {
   // root only.  Every rank derives the same grid from the byte count.
   int reduce(const void* send, void* recv, size_t bytes, int dtype, int op, int root, hipStream_t stream) {
     std::lock_guard<std::mutex> lk(mu);
-    touched.clear();
-    mscclppAmdRankView v = baseView(send, rank == root ? recv : nullptr);
-    const auto ins = registerOutput(const_cast<void*>(send), stream);
-    for (int r = 0; r < nranks; ++r) v.peerInput[r] = ins[r];
+    mscclppAmdRankView v = pullView(send, rank == root ? recv : nullptr, stream);
     const int rc = launchReduce(&v, 1, nranks, bytes, dtype, op, root, 0, 0, spinBudgetTicks(), stream);
     recordUses(stream);
     return rc;
@@ -746,13 +751,14 @@ struct ncclComm {
   // AllReduce, the per-rank block of ReduceScatter.  Every rank derives the same grid from (coll, bytes).
   int pullReduce(int coll, const void* send, void* recv, size_t bytes, int dtype, int op, int root, hipStream_t stream) {
     std::lock_guard<std::mutex> lk(mu);
-    touched.clear();
-    mscclppAmdRankView v = baseView(send, recv);
-    const auto ins = registerOutput(const_cast<void*>(send), stream);
-    for (int r = 0; r < nranks; ++r) v.peerInput[r] = ins[r];
+    mscclppAmdRankView v = pullView(send, recv, stream);
     if (coll == MSCCLPP_AMD_PULL_ALLREDUCE) {
-      const auto outs = recv == send ? ins : registerOutput(recv, stream);
-      for (int r = 0; r < nranks; ++r) v.peerOutput[r] = outs[r];
+      if (recv == send) {  // in place: the same registration
+        for (int r = 0; r < nranks; ++r) v.peerOutput[r] = const_cast<void*>(v.peerInput[r]);
+      } else {
+        const auto outs = registerOutput(recv, stream);
+        for (int r = 0; r < nranks; ++r) v.peerOutput[r] = outs[r];
+      }
     }
     const int rc = launchPullReduce(&v, 1, nranks, coll, bytes, dtype, op, root, 0, 0, spinBudgetTicks(), stream);
     recordUses(stream);
@@ -1185,6 +1191,25 @@ int groupStart();
 int groupEnd();
 void initFallbackComm(ncclComm* c);                 // collective over c's bootstrap
 void destroyFallbackComm(ncclComm* c, bool abort);
+
+// What a mscclppAmd*Launch entry point's kernel dereferences through a rank view.  kTokens is the
+// handshake plumbing (tokens, expected, peerTokens[q]); a kPeer* bit names a per-rank array.
+enum ViewField : unsigned {
+  kViewInput = 1, kViewOutput = 2, kViewScratch = 4, kViewFlags = 8, kViewPipeSems = 16, kViewErr = 32, kViewTokens = 64,
+  kViewPeerInput = 128, kViewPeerOutput = 256, kViewPeerScratch = 512,
+  kViewHandshake = kViewErr | kViewTokens,
+};
+struct ViewNeeds {
+  unsigned all = 0;       // of every view; per-rank arrays at every rank q < nranks
+  bool rank = true;       // every view's rank lies in [0, nranks)
+  int root = -1;          // the view of this rank also needs:
+  unsigned atRoot = 0;    //   these, per-rank arrays at every q
+  int peer = -1;          // every view also needs the per-rank arrays
+  unsigned atPeer = 0;    //   named here, at entry [peer] alone
+};
+// The checks every launch entry point makes before anything touches a device: views present, nviews
+// 1 or nranks, 2 <= nranks <= MSCCLPP_AMD_MAX_RANKS, and every pointer `needs` names non-null.
+bool viewsValid(const mscclppAmdRankView* views, int nviews, int nranks, const ViewNeeds& needs);
 }  // namespace host
 }  // namespace mscclpp_amd
 

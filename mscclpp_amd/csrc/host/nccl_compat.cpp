@@ -131,6 +131,30 @@ void destroyFallbackComm(ncclComm* c, bool abort) {
   c->fallback = nullptr;
 }
 
+// `v` has every pointer `f` names; its per-rank arrays at ranks [q0, q1).
+static bool viewHas(const mscclppAmdRankView& v, unsigned f, int q0, int q1) {
+  if ((f & kViewInput && !v.input) || (f & kViewOutput && !v.output) || (f & kViewScratch && !v.scratch) ||
+      (f & kViewFlags && !v.flags) || (f & kViewPipeSems && !v.pipeSems) || (f & kViewErr && !v.err) ||
+      (f & kViewTokens && (!v.tokens || !v.expected)))
+    return false;
+  for (int q = q0; q < q1; ++q)
+    if ((f & kViewTokens && !v.peerTokens[q]) || (f & kViewPeerInput && !v.peerInput[q]) ||
+        (f & kViewPeerOutput && !v.peerOutput[q]) || (f & kViewPeerScratch && !v.peerScratch[q]))
+      return false;
+  return true;
+}
+
+bool viewsValid(const mscclppAmdRankView* views, int nviews, int nranks, const ViewNeeds& needs) {
+  if (!views || nranks < 2 || nranks > MSCCLPP_AMD_MAX_RANKS || (nviews != 1 && nviews != nranks)) return false;
+  for (int i = 0; i < nviews; ++i) {
+    const mscclppAmdRankView& v = views[i];
+    if (needs.rank && (v.rank < 0 || v.rank >= nranks)) return false;
+    if (!viewHas(v, needs.all, 0, nranks) || !viewHas(v, needs.atPeer, needs.peer, needs.peer + 1)) return false;
+    if (v.rank == needs.root && !viewHas(v, needs.atRoot, 0, nranks)) return false;
+  }
+  return true;
+}
+
 }  // namespace host
 }  // namespace mscclpp_amd
 
@@ -566,16 +590,14 @@ int mscclppAmdCommDeregisterAll(ncclComm_t comm) {
 int mscclppAmdBroadcastLaunch(const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes, int root,
                               int nblocks, int nthreads, uint64_t budgetTicks, void* stream) {
   return guarded([&] {
-    if (!views || nviews < 1 || nranks < 2 || nranks > MSCCLPP_AMD_MAX_RANKS || bytes == 0) return (int)ncclInvalidArgument;
-    if (nviews != 1 && nviews != nranks) return (int)ncclInvalidArgument;
-    if (root < 0 || root >= nranks) return (int)ncclInvalidArgument;
-    for (int i = 0; i < nviews; ++i) {
-      const mscclppAmdRankView& v = views[i];
-      if (!v.output || !v.tokens || !v.expected || !v.err || !v.peerInput[root]) return (int)ncclInvalidArgument;
-      if (v.rank == root && !v.input) return (int)ncclInvalidArgument;
-      for (int q = 0; q < nranks; ++q)
-        if (!v.peerTokens[q]) return (int)ncclInvalidArgument;
-    }
+    if (bytes == 0 || root < 0 || root >= nranks) return (int)ncclInvalidArgument;
+    ViewNeeds needs;
+    needs.all = kViewOutput | kViewHandshake;
+    needs.rank = false;  // (a view's rank is only compared with the root)
+    needs.root = needs.peer = root;
+    needs.atRoot = kViewInput;
+    needs.atPeer = kViewPeerInput;
+    if (!viewsValid(views, nviews, nranks, needs)) return (int)ncclInvalidArgument;
     return mscclpp_amd::launchBroadcast(views, nviews, nranks, bytes, root, nblocks, nthreads,
                                         budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream);
   });
@@ -585,15 +607,9 @@ int mscclppAmdBroadcastLaunch(const mscclppAmdRankView* views, int nviews, int n
 int mscclppAmdAllToAllLaunch(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdAllToAllSeg* segs,
                              int nblocks, int nthreads, uint64_t budgetTicks, void* stream) {
   return guarded([&] {
-    if (!views || !segs || nviews < 1 || nranks < 2 || nranks > MSCCLPP_AMD_MAX_RANKS) return (int)ncclInvalidArgument;
-    if (nviews != 1 && nviews != nranks) return (int)ncclInvalidArgument;
-    for (int i = 0; i < nviews; ++i) {
-      const mscclppAmdRankView& v = views[i];
-      if (!v.input || !v.output || !v.tokens || !v.expected || !v.err) return (int)ncclInvalidArgument;
-      if (v.rank < 0 || v.rank >= nranks) return (int)ncclInvalidArgument;
-      for (int q = 0; q < nranks; ++q)
-        if (!v.peerTokens[q] || !v.peerInput[q]) return (int)ncclInvalidArgument;
-    }
+    ViewNeeds needs;
+    needs.all = kViewInput | kViewOutput | kViewHandshake | kViewPeerInput;
+    if (!segs || !viewsValid(views, nviews, nranks, needs)) return (int)ncclInvalidArgument;
     return mscclpp_amd::launchAllToAll(views, nviews, nranks, segs, nblocks, nthreads,
                                        budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream);
   });
@@ -605,23 +621,15 @@ int mscclppAmdAllToAllLaunch(const mscclppAmdRankView* views, int nviews, int nr
 int mscclppAmdReduceLaunch(const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes, int dtype, int op,
                            int root, int nblocks, int nthreads, uint64_t budgetTicks, void* stream) {
   return guarded([&] {
-    if (!views || nviews < 1 || nranks < 2 || nranks > MSCCLPP_AMD_MAX_RANKS) return (int)ncclInvalidArgument;
-    if (nviews != 1 && nviews != nranks) return (int)ncclInvalidArgument;
     if (root < 0 || root >= nranks) return (int)ncclInvalidArgument;
     if (dtype < 0 || dtype >= MSCCLPP_AMD_NUM_DTYPES || (op != MSCCLPP_AMD_SUM && op != MSCCLPP_AMD_MIN))
       return (int)ncclInvalidArgument;
     if (bytes == 0) return (int)ncclInvalidArgument;  // (a byte count that splits an element: launchReduce)
-    for (int i = 0; i < nviews; ++i) {
-      const mscclppAmdRankView& v = views[i];
-      if (!v.input || !v.tokens || !v.expected || !v.err) return (int)ncclInvalidArgument;
-      if (v.rank < 0 || v.rank >= nranks) return (int)ncclInvalidArgument;
-      for (int q = 0; q < nranks; ++q)
-        if (!v.peerTokens[q]) return (int)ncclInvalidArgument;
-      if (v.rank != root) continue;
-      if (!v.output) return (int)ncclInvalidArgument;
-      for (int q = 0; q < nranks; ++q)
-        if (!v.peerInput[q]) return (int)ncclInvalidArgument;
-    }
+    ViewNeeds needs;
+    needs.all = kViewInput | kViewHandshake;
+    needs.root = root;  // the only view that reads and writes user memory
+    needs.atRoot = kViewOutput | kViewPeerInput;
+    if (!viewsValid(views, nviews, nranks, needs)) return (int)ncclInvalidArgument;
     return mscclpp_amd::launchReduce(views, nviews, nranks, bytes, dtype, op, root, nblocks, nthreads,
                                      budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream);
   });
@@ -632,16 +640,10 @@ int mscclppAmdReduceLaunch(const mscclppAmdRankView* views, int nviews, int nran
 int mscclppAmdSendRecvLaunch(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdSendRecvOp* ops,
                              int nops, int nblocks, int nthreads, uint64_t budgetTicks, void* stream) {
   return guarded([&] {
-    if (!views || !ops || nviews < 1 || nranks < 2 || nranks > MSCCLPP_AMD_MAX_RANKS) return (int)ncclInvalidArgument;
-    if (nviews != 1 && nviews != nranks) return (int)ncclInvalidArgument;
+    ViewNeeds needs;
+    needs.all = kViewHandshake;
+    if (!ops || !viewsValid(views, nviews, nranks, needs)) return (int)ncclInvalidArgument;
     if (nops < 1 || nops > MSCCLPP_AMD_SENDRECV_MAX_OPS) return (int)ncclInvalidArgument;
-    for (int i = 0; i < nviews; ++i) {
-      const mscclppAmdRankView& v = views[i];
-      if (!v.tokens || !v.expected || !v.err) return (int)ncclInvalidArgument;
-      if (v.rank < 0 || v.rank >= nranks) return (int)ncclInvalidArgument;
-      for (int q = 0; q < nranks; ++q)
-        if (!v.peerTokens[q]) return (int)ncclInvalidArgument;
-    }
     for (int i = 0; i < nops; ++i) {
       const mscclppAmdSendRecvOp& o = ops[i];
       if (o.src < 0 || o.src >= nranks || o.dst < 0 || o.dst >= nranks || o.src == o.dst || o.bytes == 0)
@@ -664,25 +666,21 @@ int mscclppAmdSendRecvDefaultBlocks(uint64_t bytes) { return mscclpp_amd::sendre
 int mscclppAmdPullReduceLaunch(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes, int dtype,
                                int op, int root, int nblocks, int nthreads, uint64_t budgetTicks, void* stream) {
   return guarded([&] {
-    if (!views || nviews < 1 || nranks < 2 || nranks > MSCCLPP_AMD_MAX_RANKS) return (int)ncclInvalidArgument;
-    if (nviews != 1 && nviews != nranks) return (int)ncclInvalidArgument;
     if (coll < MSCCLPP_AMD_PULL_REDUCE || coll > MSCCLPP_AMD_PULL_ALLREDUCE) return (int)ncclInvalidArgument;
     const bool reduce = coll == MSCCLPP_AMD_PULL_REDUCE, all = coll == MSCCLPP_AMD_PULL_ALLREDUCE;
     if (reduce && (root < 0 || root >= nranks)) return (int)ncclInvalidArgument;
     if (op != MSCCLPP_AMD_MAX && op != MSCCLPP_AMD_AVG) return (int)ncclInvalidArgument;  // SUM / MIN: their own kernels
     if (bytes == 0) return (int)ncclInvalidArgument;  // (the dtype codes and a split element: launchPullReduce)
+    // what moves data: every view, but for Reduce the root's alone (the others read and write no user memory)
+    const unsigned moves = kViewOutput | kViewPeerInput | (all ? kViewPeerOutput : 0u);
+    ViewNeeds needs;
+    needs.all = kViewInput | kViewHandshake | (reduce ? 0u : moves);
+    if (reduce) needs.root = root, needs.atRoot = moves;
+    if (!viewsValid(views, nviews, nranks, needs)) return (int)ncclInvalidArgument;
     unsigned seen = 0;
-    for (int i = 0; i < nviews; ++i) {
-      const mscclppAmdRankView& v = views[i];
-      if (!v.input || !v.tokens || !v.expected || !v.err) return (int)ncclInvalidArgument;
-      if (v.rank < 0 || v.rank >= nranks || (seen >> v.rank) & 1u) return (int)ncclInvalidArgument;
-      seen |= 1u << v.rank;
-      for (int q = 0; q < nranks; ++q)
-        if (!v.peerTokens[q]) return (int)ncclInvalidArgument;
-      if (reduce && v.rank != root) continue;  // reads and writes no user memory
-      if (!v.output) return (int)ncclInvalidArgument;
-      for (int q = 0; q < nranks; ++q)
-        if (!v.peerInput[q] || (all && !v.peerOutput[q])) return (int)ncclInvalidArgument;
+    for (int i = 0; i < nviews; ++i) {  // no rank twice
+      if ((seen >> views[i].rank) & 1u) return (int)ncclInvalidArgument;
+      seen |= 1u << views[i].rank;
     }
     return mscclpp_amd::launchPullReduce(views, nviews, nranks, coll, bytes, dtype, op, root, nblocks, nthreads,
                                          budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream);

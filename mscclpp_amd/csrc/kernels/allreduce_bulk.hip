@@ -19,8 +19,8 @@
 //  * Waits are relaxed system-scope polls followed by one system-scope acquire, bounded in time.
 #include <cstdlib>
 
-#include "common.hpp"
 #include "handshake.hpp"
+#include "launch.hpp"
 
 namespace mscclpp_amd {
 
@@ -503,13 +503,6 @@ __global__ void __launch_bounds__(512) allreduceRsAgPipelineKernel(Views<NV> vie
   }
 }
 
-static thread_local int g_launch_status = 0;
-
-// Each workgroup addresses its sub-range of a buffer from one buffer resource (32-bit offsets): a
-// launch whose per-workgroup range would exceed that is refused (ncclInvalidUsage) -- more
-// workgroups carry it (every default shape does up to hundreds of GiB).
-constexpr uint64_t kBlkOffsetLimit = 0xFFFFFFFFull - 64;
-
 size_t bulkScratchRequired(int nranks, size_t bytes, size_t maxScratch, BulkGeom* out, int nblocks) {
   BulkGeom g{};
   g.trace = g_mscclppAmdTrace;
@@ -520,87 +513,59 @@ size_t bulkScratchRequired(int nranks, size_t bytes, size_t maxScratch, BulkGeom
   // resource the reduce step reads all n regions through (source q at q * pass)
   uint64_t pass = g.slice;
   uint64_t cap = maxScratch / (uint64_t)nranks;
-  const uint64_t cap32 = (0xFFFFFFFFull - 64) / (uint64_t)nranks;
+  const uint64_t cap32 = kBlkOffsetLimit / (uint64_t)nranks;
   if (cap > cap32) cap = cap32;
   if (pass > cap) pass = cap / ((uint64_t)16 * nblocks) * ((uint64_t)16 * nblocks);
   if (pass == 0) return 0;
   g.pass = pass;
   g.npasses = (uint32_t)((g.slice + pass - 1) / pass);
-  g.blk = ((pass + nblocks - 1) / nblocks + 15) & ~15ull;
+  g.blk = blockBytes(pass, (uint32_t)nblocks);
   if (out) *out = g;
   return (size_t)(nranks * pass);
 }
 
-template <int DT, int OP, int NV, int ORDER>
-static void launchBulkT(const Views<NV>& vw, int nviews, const BulkGeom& g, int nranks, int nblocks, int nthreads, uint64_t budget,
-                        hipStream_t s, int mode) {
-  if (!grid_coresident(allreduceBulkKernel<DT, OP, NV, ORDER, 0>, nthreads, (long)nblocks * nviews)) {
-    g_launch_status = 5;  // ncclInvalidUsage: the grid cannot be resident at once: its handshakes would deadlock
-    return;
-  }
-  if (mode == 0)
-    hipLaunchKernelGGL((allreduceBulkKernel<DT, OP, NV, ORDER, 0>), dim3(nblocks, nviews), dim3(nthreads), 0, s, vw, g,
-                       nranks, budget);
-  else if (mode == 1)
-    hipLaunchKernelGGL((allreduceBulkKernel<DT, OP, NV, ORDER, 1>), dim3(nblocks, nviews), dim3(nthreads), 0, s, vw, g,
-                       nranks, budget);
-  else if constexpr (ORDER == 0 && OP == kSum && (DT == kF16 || DT == kF32))
-    // AllGather moves bytes only: one instantiation per element width is enough
-    hipLaunchKernelGGL((allreduceBulkKernel<DT, OP, NV, ORDER, 2>), dim3(nblocks, nviews), dim3(nthreads), 0, s, vw, g,
-                       nranks, budget);
+// mode 0 AllReduce (bytes = whole buffer), 1 ReduceScatter / 2 AllGather (bytes = n * block, block % 16 == 0).
+// Co-residency is asked of the AllReduce instantiation, whatever the mode.
+template <int DT, int OP, int ORDER>
+static int launchBulkOrder(const mscclppAmdRankView* views, int nviews, const BulkGeom& g, int nranks, int nblocks,
+                           int nthreads, uint64_t budget, hipStream_t s, int mode) {
+  auto go = [&](auto k1, auto kN) {
+    return launchViews(allreduceBulkKernel<DT, OP, 1, ORDER, 0>, allreduceBulkKernel<DT, OP, kMaxRanks, ORDER, 0>, k1, kN,
+                       views, nviews, nblocks, nthreads, s, g, nranks, budget);
+  };
+  if (mode == 0) return go(allreduceBulkKernel<DT, OP, 1, ORDER, 0>, allreduceBulkKernel<DT, OP, kMaxRanks, ORDER, 0>);
+  if (mode == 1) return go(allreduceBulkKernel<DT, OP, 1, ORDER, 1>, allreduceBulkKernel<DT, OP, kMaxRanks, ORDER, 1>);
+  // AllGather moves bytes only: one instantiation per element width is enough
+  if constexpr (ORDER == 0 && OP == kSum && (DT == kF16 || DT == kF32))
+    return go(allreduceBulkKernel<DT, OP, 1, ORDER, 2>, allreduceBulkKernel<DT, OP, kMaxRanks, ORDER, 2>);
+  return 4;  // (not reached: launchCollectiveBulk maps an AllGather to one of those)
 }
 
 template <int DT, int OP>
-static void launchBulk(const mscclppAmdRankView* views, int nviews, const BulkGeom& g, int nranks, int nblocks,
-                       int nthreads, uint64_t budget, hipStream_t s, int order, int mode) {
-  if (nviews == 1) {
-    Views<1> vw;
-    vw.v[0] = views[0];
-    if (order == 0)
-      launchBulkT<DT, OP, 1, 0>(vw, nviews, g, nranks, nblocks, nthreads, budget, s, mode);
-    else
-      launchBulkT<DT, OP, 1, 1>(vw, nviews, g, nranks, nblocks, nthreads, budget, s, mode);
-  } else {
-    Views<kMaxRanks> vw{};
-    for (int i = 0; i < nviews; ++i) vw.v[i] = views[i];
-    if (order == 0)
-      launchBulkT<DT, OP, kMaxRanks, 0>(vw, nviews, g, nranks, nblocks, nthreads, budget, s, mode);
-    else
-      launchBulkT<DT, OP, kMaxRanks, 1>(vw, nviews, g, nranks, nblocks, nthreads, budget, s, mode);
-  }
-}
-
-// mode 0 AllReduce (bytes = whole buffer), 1 ReduceScatter / 2 AllGather (bytes = n * block, block % 16 == 0)
-template <int DT, int OP, int NV>
-static void launchZeroCopyT(const Views<NV>& vw, int nviews, const BulkGeom& g, int nranks, int nblocks, int nthreads,
-                            uint64_t budget, hipStream_t s) {
-  if (!grid_coresident(allreduceZeroCopyKernel<DT, OP, NV>, nthreads, (long)nblocks * nviews)) {
-    g_launch_status = 5;  // ncclInvalidUsage: handshakes of a non-resident grid would deadlock
-    return;
-  }
-  hipLaunchKernelGGL((allreduceZeroCopyKernel<DT, OP, NV>), dim3(nblocks, nviews), dim3(nthreads), 0, s, vw, g, nranks,
-                     budget);
+static int launchBulk(const mscclppAmdRankView* views, int nviews, const BulkGeom& g, int nranks, int nblocks,
+                      int nthreads, uint64_t budget, hipStream_t s, int order, int mode) {
+  return order == 0 ? launchBulkOrder<DT, OP, 0>(views, nviews, g, nranks, nblocks, nthreads, budget, s, mode)
+                    : launchBulkOrder<DT, OP, 1>(views, nviews, g, nranks, nblocks, nthreads, budget, s, mode);
 }
 
 template <int DT, int OP>
-static void launchZeroCopy(const mscclppAmdRankView* views, int nviews, const BulkGeom& g, int nranks, int nblocks,
-                           int nthreads, uint64_t budget, hipStream_t s) {
-  if (nviews == 1) {
-    Views<1> vw;
-    vw.v[0] = views[0];
-    launchZeroCopyT<DT, OP, 1>(vw, nviews, g, nranks, nblocks, nthreads, budget, s);
-  } else {
-    Views<kMaxRanks> vw{};
-    for (int i = 0; i < nviews; ++i) vw.v[i] = views[i];
-    launchZeroCopyT<DT, OP, kMaxRanks>(vw, nviews, g, nranks, nblocks, nthreads, budget, s);
-  }
+static int launchZeroCopy(const mscclppAmdRankView* views, int nviews, const BulkGeom& g, int nranks, int nblocks,
+                          int nthreads, uint64_t budget, hipStream_t s) {
+  return launchViews(allreduceZeroCopyKernel<DT, OP, 1>, allreduceZeroCopyKernel<DT, OP, kMaxRanks>, views, nviews,
+                     nblocks, nthreads, s, g, nranks, budget);
+}
+
+template <int DT, int OP>
+static int launchTestK5(const mscclppAmdRankView* views, int nviews, const BulkGeom& g, int nranks, int nblocks,
+                        int nthreads, uint64_t budget, hipStream_t s) {
+  return launchViews(allreduceTestK5Kernel<DT, OP, 1>, allreduceTestK5Kernel<DT, OP, kMaxRanks>, views, nviews, nblocks,
+                     nthreads, s, g, nranks, budget);
 }
 
 int launchCollectiveBulk(int mode, int algo, const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes,
                          int dtype, int op, int nblocks, int nthreads, uint64_t budget, hipStream_t s) {
   if (nblocks <= 0) nblocks = 64;
-  if (nthreads <= 0) nthreads = 512;
-  if (nblocks > kMaxChannels || nthreads > 512 || nthreads % 64 || nthreads < 64) return 4;
+  if (!launchShapeOk(nblocks, kMaxChannels, nthreads)) return 4;
   if (algo == MSCCLPP_AMD_ALGO_TEST_K5) {
     // (the harness launches 24 x 1024, allreduce_test.cu:1126-1129; here the channel defaults apply)
     if (mode != 0 || (dtype != kI32 && dtype != kU32)) return 4;
@@ -613,39 +578,14 @@ int launchCollectiveBulk(int mode, int algo, const mscclppAmdRankView* views, in
     g.slice = bytes / nranks;
     g.pass = g.slice;
     g.npasses = 1;
-    g.blk = ((g.slice + nblocks - 1) / nblocks + 15) & ~15ull;
+    g.blk = blockBytes(g.slice, (uint32_t)nblocks);
     if (g.blk > kBlkOffsetLimit) return 5;  // more workgroups needed: one workgroup's range is one descriptor
-    g_launch_status = 0;
-    auto go = [&](auto kern) {
-      if (!grid_coresident(kern, nthreads, (long)nblocks * nviews)) {
-        g_launch_status = 5;
-        return;
-      }
-      if (nviews == 1) {
-        Views<1> vw;
-        vw.v[0] = views[0];
-        hipLaunchKernelGGL(kern, dim3(nblocks, nviews), dim3(nthreads), 0, s, vw, g, nranks, budget);
-      }
-    };
-    auto goN = [&](auto kern) {
-      if (!grid_coresident(kern, nthreads, (long)nblocks * nviews)) {
-        g_launch_status = 5;
-        return;
-      }
-      Views<kMaxRanks> vw{};
-      for (int i = 0; i < nviews; ++i) vw.v[i] = views[i];
-      hipLaunchKernelGGL(kern, dim3(nblocks, nviews), dim3(nthreads), 0, s, vw, g, nranks, budget);
-    };
-    const bool u32 = dtype == kU32, mn = op == kMin;
-    if (nviews == 1) {
-      if (u32) mn ? go(allreduceTestK5Kernel<kU32, kMin, 1>) : go(allreduceTestK5Kernel<kU32, kSum, 1>);
-      else mn ? go(allreduceTestK5Kernel<kI32, kMin, 1>) : go(allreduceTestK5Kernel<kI32, kSum, 1>);
-    } else {
-      if (u32) mn ? goN(allreduceTestK5Kernel<kU32, kMin, kMaxRanks>) : goN(allreduceTestK5Kernel<kU32, kSum, kMaxRanks>);
-      else mn ? goN(allreduceTestK5Kernel<kI32, kMin, kMaxRanks>) : goN(allreduceTestK5Kernel<kI32, kSum, kMaxRanks>);
-    }
-    if (g_launch_status) return g_launch_status;
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    const bool mn = op == kMin;
+    if (dtype == kU32)
+      return mn ? launchTestK5<kU32, kMin>(views, nviews, g, nranks, nblocks, nthreads, budget, s)
+                : launchTestK5<kU32, kSum>(views, nviews, g, nranks, nblocks, nthreads, budget, s);
+    return mn ? launchTestK5<kI32, kMin>(views, nviews, g, nranks, nblocks, nthreads, budget, s)
+              : launchTestK5<kI32, kSum>(views, nviews, g, nranks, nblocks, nthreads, budget, s);
   }
   if (algo == MSCCLPP_AMD_ALGO_RSAG_ZC) {
     if (mode != 0) return 4;
@@ -655,12 +595,9 @@ int launchCollectiveBulk(int mode, int algo, const mscclppAmdRankView* views, in
     g.slice = ((bytes + nranks - 1) / nranks + 15) & ~15ull;
     g.pass = g.slice;
     g.npasses = 1;
-    g.blk = ((g.slice + nblocks - 1) / nblocks + 15) & ~15ull;
+    g.blk = blockBytes(g.slice, (uint32_t)nblocks);
     if (g.blk > kBlkOffsetLimit) return 5;
-    g_launch_status = 0;
     MSCCLPP_AMD_DISPATCH_ALL(dtype, op, launchZeroCopy, views, nviews, g, nranks, nblocks, nthreads, budget, s);
-    if (g_launch_status) return g_launch_status;
-    return hipGetLastError() == hipSuccess ? 0 : 1;
   }
   if (mode != 0 && (bytes % ((size_t)16 * nranks))) return 5;
   BulkGeom g{};
@@ -676,10 +613,7 @@ int launchCollectiveBulk(int mode, int algo, const mscclppAmdRankView* views, in
     dtype = elem_bytes(dtype) == 2 ? kF16 : kF32;
     op = kSum;
   }
-  g_launch_status = 0;
   MSCCLPP_AMD_DISPATCH_ALL(dtype, op, launchBulk, views, nviews, g, nranks, nblocks, nthreads, budget, s, order, mode);
-  if (g_launch_status) return g_launch_status;
-  return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
 int launchBroadcast(const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes, int root, int nblocks,
@@ -688,47 +622,20 @@ int launchBroadcast(const mscclppAmdRankView* views, int nviews, int nranks, siz
     const uint64_t want = (bytes + (256u << 10) - 1) / (256u << 10);
     nblocks = (int)(want < 8 ? 8 : want > 128 ? 128 : want);
   }
-  if (nthreads <= 0) nthreads = 512;
-  if (nblocks > kMaxChannels || nthreads > 512 || nthreads % 64 || nthreads < 64) return 4;
+  if (!launchShapeOk(nblocks, kMaxChannels, nthreads)) return 4;
   if (root < 0 || root >= nranks || bytes == 0) return 4;
-  const uint64_t blk = ((bytes + nblocks - 1) / nblocks + 15) & ~15ull;
+  const uint64_t blk = blockBytes(bytes, (uint32_t)nblocks);
   if (blk > kBlkOffsetLimit) return 5;
-  auto go = [&](auto kern, auto vw) {
-    if (!grid_coresident(kern, nthreads, (long)nblocks * nviews)) return 5;
-    hipLaunchKernelGGL(kern, dim3(nblocks, nviews), dim3(nthreads), 0, s, vw, (uint64_t)bytes, blk, nranks, root,
-                       budget);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
-  };
-  if (nviews == 1) {
-    Views<1> vw;
-    vw.v[0] = views[0];
-    return go(broadcastKernel<1, 4>, vw);
-  }
-  Views<kMaxRanks> vw{};
-  for (int i = 0; i < nviews; ++i) vw.v[i] = views[i];
-  return go(broadcastKernel<kMaxRanks, 4>, vw);
+  return launchViews(broadcastKernel<1, 4>, broadcastKernel<kMaxRanks, 4>, views, nviews, nblocks, nthreads, s,
+                     (uint64_t)bytes, blk, nranks, root, budget);
 }
 
+// The put, reduce and recv roles (2 * R workgroups) wait on each other inside the launch: all must be resident.
 template <int DT, int OP>
-static void launchPipeline(const mscclppAmdRankView* views, int nviews, const PipeGeom& g, int nranks, int nthreads,
-                           uint64_t budget, hipStream_t s) {
-  auto go = [&](auto kern, auto vw) {
-    const long blocks = (long)(g.R + g.R) * nviews;
-    if (!grid_coresident(kern, nthreads, blocks)) {
-      g_launch_status = 5;  // the roles wait on each other inside the launch: all must be resident
-      return;
-    }
-    hipLaunchKernelGGL(kern, dim3(g.R + g.R, nviews), dim3(nthreads), 0, s, vw, g, nranks, budget);
-  };
-  if (nviews == 1) {
-    Views<1> vw;
-    vw.v[0] = views[0];
-    go(allreduceRsAgPipelineKernel<DT, OP, 1>, vw);
-  } else {
-    Views<kMaxRanks> vw{};
-    for (int i = 0; i < nviews; ++i) vw.v[i] = views[i];
-    go(allreduceRsAgPipelineKernel<DT, OP, kMaxRanks>, vw);
-  }
+static int launchPipeline(const mscclppAmdRankView* views, int nviews, const PipeGeom& g, int nranks, int nthreads,
+                          uint64_t budget, hipStream_t s) {
+  return launchViews(allreduceRsAgPipelineKernel<DT, OP, 1>, allreduceRsAgPipelineKernel<DT, OP, kMaxRanks>, views,
+                     nviews, (int)(g.R + g.R), nthreads, s, g, nranks, budget);
 }
 
 // R reduce workgroups (nblocks, even, 2..128; default 32) of nthreads (default 512) lanes; the
@@ -736,8 +643,7 @@ static void launchPipeline(const mscclppAmdRankView* views, int nviews, const Pi
 int launchAllReducePipeline(const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes, int dtype, int op,
                             int nblocks, int nthreads, uint64_t budget, hipStream_t s) {
   if (nblocks <= 0) nblocks = 32;
-  if (nthreads <= 0) nthreads = 512;
-  if (nblocks % 2 || nblocks < 2 || nblocks > 128 || nthreads > 512 || nthreads % 64 || nthreads < 64) return 4;
+  if (nblocks % 2 || nblocks < 2 || !launchShapeOk(nblocks, 128, nthreads)) return 4;
   if (dtype != kF16 && dtype != kBF16 && dtype != kF32 && dtype != kI32 && dtype != kU32) return 4;
   PipeGeom g{};
   g.bytes = bytes;
@@ -757,24 +663,8 @@ int launchAllReducePipeline(const mscclppAmdRankView* views, int nviews, int nra
   for (int i = 1; i < nviews; ++i) minScratch = views[i].scratchBytes < minScratch ? views[i].scratchBytes : minScratch;
   uint64_t D = minScratch / stage;
   g.D = (uint32_t)(D > g.nIters ? (g.nIters ? g.nIters : 1) : D);
-  g_launch_status = 0;
-  if (dtype == kF16)
-    op == kMin ? launchPipeline<kF16, kMin>(views, nviews, g, nranks, nthreads, budget, s)
-               : launchPipeline<kF16, kSum>(views, nviews, g, nranks, nthreads, budget, s);
-  else if (dtype == kBF16)
-    op == kMin ? launchPipeline<kBF16, kMin>(views, nviews, g, nranks, nthreads, budget, s)
-               : launchPipeline<kBF16, kSum>(views, nviews, g, nranks, nthreads, budget, s);
-  else if (dtype == kF32)
-    op == kMin ? launchPipeline<kF32, kMin>(views, nviews, g, nranks, nthreads, budget, s)
-               : launchPipeline<kF32, kSum>(views, nviews, g, nranks, nthreads, budget, s);
-  else if (dtype == kI32)
-    op == kMin ? launchPipeline<kI32, kMin>(views, nviews, g, nranks, nthreads, budget, s)
-               : launchPipeline<kI32, kSum>(views, nviews, g, nranks, nthreads, budget, s);
-  else
-    op == kMin ? launchPipeline<kU32, kMin>(views, nviews, g, nranks, nthreads, budget, s)
-               : launchPipeline<kU32, kSum>(views, nviews, g, nranks, nthreads, budget, s);
-  if (g_launch_status) return g_launch_status;
-  return hipGetLastError() == hipSuccess ? 0 : 1;
+  // (any op but MIN runs as SUM)
+  MSCCLPP_AMD_DISPATCH(dtype, op == kMin ? kMin : kSum, launchPipeline, views, nviews, g, nranks, nthreads, budget, s);
 }
 
 int launchAllReduceBulk(int algo, const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes, int dtype,

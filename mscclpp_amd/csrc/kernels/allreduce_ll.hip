@@ -20,7 +20,7 @@
 // loads issued for all peers before any spin; peer
 // pointers come from kernel arguments (scalar loads), not from channel handles copied to LDS; loops
 // over peers are unrolled to the 8-GPU maximum with predicates so the per-peer values stay in VGPRs.
-#include "common.hpp"
+#include "launch.hpp"
 
 namespace mscclpp_amd {
 
@@ -626,77 +626,34 @@ size_t ll8ScratchRequired(int nranks, size_t bytes, int dtype) {
   return 2 * half;
 }
 
-static thread_local int g_ll_launch_status = 0;
-
-template <int DT, int OP, int NV, int V = 0>
-static void launchLL16T(const Views<NV>& vw, int nviews, const LL16Geom& g, int nranks, int nblocks, int nthreads, uint64_t budget,
-                        hipStream_t s) {
-  if (!grid_coresident(allreduceLL16Kernel<DT, OP, NV, V>, nthreads, (long)nblocks * nviews)) {
-    g_ll_launch_status = 5;  // ncclInvalidUsage: the grid cannot be resident at once: its packet waits would deadlock
-    return;
-  }
-  hipLaunchKernelGGL((allreduceLL16Kernel<DT, OP, NV, V>), dim3(nblocks, nviews), dim3(nthreads), 0, s, vw, g, nranks, budget);
-}
-template <int DT, int OP, int NV, int V = 0>
-static void launchLL8T(const Views<NV>& vw, int nviews, const LL8Geom& g, int nranks, int nblocks, int nthreads, uint64_t budget,
-                       hipStream_t s) {
-  if (!grid_coresident(allreduceLL8Kernel<DT, OP, NV, V>, nthreads, (long)nblocks * nviews)) {
-    g_ll_launch_status = 5;  // ncclInvalidUsage: the grid cannot be resident at once: its packet waits would deadlock
-    return;
-  }
-  hipLaunchKernelGGL((allreduceLL8Kernel<DT, OP, NV, V>), dim3(nblocks, nviews), dim3(nthreads), 0, s, vw, g, nranks, budget);
-}
-
-template <int DT, int OP>
-static void launchLL16(const mscclppAmdRankView* views, int nviews, const LL16Geom& g, int nranks, int nblocks,
-                       int nthreads, uint64_t budget, hipStream_t s) {
-  if (nviews == 1) {
-    Views<1> vw;
-    vw.v[0] = views[0];
-    launchLL16T<DT, OP, 1>(vw, nviews, g, nranks, nblocks, nthreads, budget, s);
-  } else {
-    Views<kMaxRanks> vw{};
-    for (int i = 0; i < nviews; ++i) vw.v[i] = views[i];
-    launchLL16T<DT, OP, kMaxRanks>(vw, nviews, g, nranks, nblocks, nthreads, budget, s);
-  }
+// (a grid that cannot be resident at once is refused: its packet waits would deadlock)
+template <int DT, int OP, int V = 0>
+static int launchLL16(const mscclppAmdRankView* views, int nviews, const LL16Geom& g, int nranks, int nblocks,
+                      int nthreads, uint64_t budget, hipStream_t s) {
+  return launchViews(allreduceLL16Kernel<DT, OP, 1, V>, allreduceLL16Kernel<DT, OP, kMaxRanks, V>, views, nviews, nblocks,
+                     nthreads, s, g, nranks, budget);
 }
 template <int DT, int OP, int V = 0>
-static void launchLL8(const mscclppAmdRankView* views, int nviews, const LL8Geom& g, int nranks, int nblocks,
-                      int nthreads, uint64_t budget, hipStream_t s) {
-  if (nviews == 1) {
-    Views<1> vw;
-    vw.v[0] = views[0];
-    launchLL8T<DT, OP, 1, V>(vw, nviews, g, nranks, nblocks, nthreads, budget, s);
-  } else {
-    Views<kMaxRanks> vw{};
-    for (int i = 0; i < nviews; ++i) vw.v[i] = views[i];
-    launchLL8T<DT, OP, kMaxRanks, V>(vw, nviews, g, nranks, nblocks, nthreads, budget, s);
-  }
+static int launchLL8(const mscclppAmdRankView* views, int nviews, const LL8Geom& g, int nranks, int nblocks,
+                     int nthreads, uint64_t budget, hipStream_t s) {
+  return launchViews(allreduceLL8Kernel<DT, OP, 1, V>, allreduceLL8Kernel<DT, OP, kMaxRanks, V>, views, nviews, nblocks,
+                     nthreads, s, g, nranks, budget);
 }
 // mscclpp-test allreduce6 / allreduce7 and the benchmark's allreduce2: the LL16 kernel with the harness
 // geometry and the benchmark's sum order (V 2048).  int32 for the harness kernels; fp16 and fp32 as the
 // benchmark builds allreduce2 with TYPE=__half / float.
 template <int DT, int OP>
-static void launchTestK6(const mscclppAmdRankView* views, int nviews, const LL16Geom& g, int nranks, int nblocks,
-                         int nthreads, uint64_t budget, hipStream_t s) {
-  if constexpr ((DT == kI32 || DT == kU32 || DT == kF16 || DT == kF32) && OP == kSum) {
-    if (nviews == 1) {
-      Views<1> vw;
-      vw.v[0] = views[0];
-      launchLL16T<DT, OP, 1, 2048>(vw, nviews, g, nranks, nblocks, nthreads, budget, s);
-    } else {
-      Views<kMaxRanks> vw{};
-      for (int i = 0; i < nviews; ++i) vw.v[i] = views[i];
-      launchLL16T<DT, OP, kMaxRanks, 2048>(vw, nviews, g, nranks, nblocks, nthreads, budget, s);
-    }
-  } else {
-    launchLL16<DT, OP>(views, nviews, g, nranks, nblocks, nthreads, budget, s);  // int32 MIN: order-free
-  }
+static int launchTestK6(const mscclppAmdRankView* views, int nviews, const LL16Geom& g, int nranks, int nblocks,
+                        int nthreads, uint64_t budget, hipStream_t s) {
+  if constexpr ((DT == kI32 || DT == kU32 || DT == kF16 || DT == kF32) && OP == kSum)
+    return launchLL16<DT, OP, 2048>(views, nviews, g, nranks, nblocks, nthreads, budget, s);
+  else
+    return launchLL16<DT, OP>(views, nviews, g, nranks, nblocks, nthreads, budget, s);  // int32 MIN: order-free
 }
 template <int DT, int OP>
-static void launchTestK2(const mscclppAmdRankView* views, int nviews, const LL8Geom& g, int nranks, int nblocks,
-                         int nthreads, uint64_t budget, hipStream_t s) {
-  launchLL8<DT, OP, 1024>(views, nviews, g, nranks, nblocks, nthreads, budget, s);
+static int launchTestK2(const mscclppAmdRankView* views, int nviews, const LL8Geom& g, int nranks, int nblocks,
+                        int nthreads, uint64_t budget, hipStream_t s) {
+  return launchLL8<DT, OP, 1024>(views, nviews, g, nranks, nblocks, nthreads, budget, s);
 }
 
 // Default grids.  LL16: a multiple of the peer count (allreduce_packet.cu:164; its defaults, :180-212,
@@ -742,14 +699,13 @@ static void ll8Defaults(int nranks, size_t bytes, int& nblocks, int& nthreads) {
 
 int launchAllReduceLL(int algo, const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes, int dtype,
                       int op, int nblocks, int nthreads, uint64_t budget, hipStream_t s) {
-  g_ll_launch_status = 0;
   if (algo == MSCCLPP_AMD_ALGO_PACKET) {
     // an explicit grid narrower than the peer count is an invalid argument (allreduce_packet.cu:238-241)
     if (nblocks > 0 && nblocks < nranks - 1) return 4;
     // ... and so is one above the flag slots, whatever rounding it down to the peer count would leave
     if (nblocks > kFlagSlots) return 4;
     ll16Defaults(nranks, bytes, nblocks, nthreads);
-    if (nblocks > kFlagSlots || nthreads > 512 || nthreads % 64) return 4;
+    if (!launchShapeOk(nblocks, kFlagSlots, nthreads)) return 4;
     LL16Geom g = ll16Geometry(nranks, bytes, dtype);
     if (g.W == 0) return 4;
     if (!ll16Fits(nranks, g)) return 5;
@@ -758,26 +714,26 @@ int launchAllReduceLL(int algo, const mscclppAmdRankView* views, int nviews, int
         return 5;
     g.hbOdd = views[0].scratchBytes / 2;  // (flag % numScratchBuff) ? scratchBufferSize / 2 : 0 (:60)
     g.hbEven = 0;
-    MSCCLPP_AMD_DISPATCH_ALL(dtype, op,launchLL16, views, nviews, g, nranks, nblocks, nthreads, budget, s);
-  } else if (algo == MSCCLPP_AMD_ALGO_TEST_K2) {
+    MSCCLPP_AMD_DISPATCH_ALL(dtype, op, launchLL16, views, nviews, g, nranks, nblocks, nthreads, budget, s);
+  }
+  if (algo == MSCCLPP_AMD_ALGO_TEST_K2) {
     // harness default (allreduce_test.cu:1142-1145): (nRanksPerNode - 1) blocks of 1024 threads ->
     // twice as many 512-lane workgroups here
-    if (nthreads <= 0) nthreads = 512;
     if (nblocks <= 0) nblocks = 2 * (nranks - 1);
-    if (nblocks > kFlagSlots || nthreads > 512 || nthreads % 64) return 4;
+    if (!launchShapeOk(nblocks, kFlagSlots, nthreads)) return 4;
     if (dtype != kI32 && dtype != kU32) return 4;  // an int32 AllReduce
     LL8Geom g;
     if (!testK2Geometry(nranks, bytes, &g) || !ll8Fits(nranks, g)) return 5;
     for (int i = 0; i < nviews; ++i)
       if (views[i].scratchBytes < testK2ScratchRequired(nranks, bytes)) return 5;
     MSCCLPP_AMD_DISPATCH(dtype, op, launchTestK2, views, nviews, g, nranks, nblocks, nthreads, budget, s);
-  } else if (algo == MSCCLPP_AMD_ALGO_TEST_K6 || algo == MSCCLPP_AMD_ALGO_TEST_K7) {
+  }
+  if (algo == MSCCLPP_AMD_ALGO_TEST_K6 || algo == MSCCLPP_AMD_ALGO_TEST_K7) {
     // harness defaults (allreduce_test.cu:1134-1141): k6 21 x 512, k7 28 x 1024 -> 512-lane waves here
-    if (nthreads <= 0) nthreads = 512;
     if (nblocks <= 0) nblocks = algo == MSCCLPP_AMD_ALGO_TEST_K6 ? 21 : 28;
     nblocks = nblocks / (nranks - 1) * (nranks - 1);
     if (nblocks < nranks - 1) nblocks = nranks - 1;
-    if (nblocks > kFlagSlots || nthreads > 512 || nthreads % 64) return 4;
+    if (!launchShapeOk(nblocks, kFlagSlots, nthreads)) return 4;
     // the mscclpp-test kernels are int32 AllReduces; k6 also runs fp16 / fp32 SUM as the benchmark's
     // allreduce2 (python/mscclpp_benchmark/allreduce.cu:223-289, TYPE=__half / float) does
     const bool benchTyped = algo == MSCCLPP_AMD_ALGO_TEST_K6 && (dtype == kF16 || dtype == kF32) && op == kSum;
@@ -786,24 +742,17 @@ int launchAllReduceLL(int algo, const mscclppAmdRankView* views, int nviews, int
     if (!testLLGeometry(nranks, bytes, &g) || !ll16Fits(nranks, g)) return 5;
     for (int i = 0; i < nviews; ++i)
       if (views[i].scratchBytes < testLLScratchRequired(nranks, bytes)) return 5;
-    if (dtype == kF16)
-      launchTestK6<kF16, kSum>(views, nviews, g, nranks, nblocks, nthreads, budget, s);
-    else if (dtype == kF32)
-      launchTestK6<kF32, kSum>(views, nviews, g, nranks, nblocks, nthreads, budget, s);
-    else
-      MSCCLPP_AMD_DISPATCH(dtype, op, launchTestK6, views, nviews, g, nranks, nblocks, nthreads, budget, s);
-  } else {
-    ll8Defaults(nranks, bytes, nblocks, nthreads);
-    if (nblocks > kFlagSlots || nthreads > 512 || nthreads % 64) return 4;
-    const LL8Geom g = ll8Geometry(bytes, dtype);
-    if (g.W == 0) return 4;
-    if (!ll8Fits(nranks, g)) return 5;
-    for (int i = 0; i < nviews; ++i)
-      if (views[i].scratchBytes < ll8ScratchRequired(nranks, bytes, dtype)) return 5;
-    MSCCLPP_AMD_DISPATCH_ALL(dtype, op,launchLL8, views, nviews, g, nranks, nblocks, nthreads, budget, s);
+    // (fp16 / fp32 come here with SUM only: benchTyped)
+    MSCCLPP_AMD_DISPATCH(dtype, op, launchTestK6, views, nviews, g, nranks, nblocks, nthreads, budget, s);
   }
-  if (g_ll_launch_status) return g_ll_launch_status;
-  return hipGetLastError() == hipSuccess ? 0 : 1;
+  ll8Defaults(nranks, bytes, nblocks, nthreads);
+  if (!launchShapeOk(nblocks, kFlagSlots, nthreads)) return 4;
+  const LL8Geom g = ll8Geometry(bytes, dtype);
+  if (g.W == 0) return 4;
+  if (!ll8Fits(nranks, g)) return 5;
+  for (int i = 0; i < nviews; ++i)
+    if (views[i].scratchBytes < ll8ScratchRequired(nranks, bytes, dtype)) return 5;
+  MSCCLPP_AMD_DISPATCH_ALL(dtype, op, launchLL8, views, nviews, g, nranks, nblocks, nthreads, budget, s);
 }
 
 }  // namespace mscclpp_amd
@@ -821,7 +770,6 @@ extern "C" int mscclppAmdDiagAllReduceLL(int algo, const mscclppAmdRankView* vie
   if (nviews != nranks || nranks < 2 || nranks > kMaxRanks) return 4;
   Views<kMaxRanks> vw{};
   for (int i = 0; i < nviews; ++i) vw.v[i] = views[i];
-  g_ll_launch_status = 0;
   if (algo == MSCCLPP_AMD_ALGO_PACKET) {
     // an explicit grid narrower than the peer count is an invalid argument (allreduce_packet.cu:238-241)
     if (nblocks > 0 && nblocks < nranks - 1) return 4;
@@ -830,20 +778,21 @@ extern "C" int mscclppAmdDiagAllReduceLL(int algo, const mscclppAmdRankView* vie
     if (views[0].scratchBytes < ll16ScratchRequired(nranks, bytes, kF16)) return 5;
     g.hbOdd = views[0].scratchBytes / 2;
     g.hbEven = 0;
-#define LV(VV) if (variant == VV) launchLL16T<kF16, kSum, kMaxRanks, VV>(vw, nviews, g, nranks, nblocks, nthreads, budget, s);
+    auto go = [&](auto kern) { return launchResident(kern, kern, nblocks, nviews, nthreads, s, vw, g, nranks, budget); };
+#define LV(VV) if (variant == VV) return go(allreduceLL16Kernel<kF16, kSum, kMaxRanks, VV>);
     LV(0) LV(4) LV(8) LV(12) LV(16) LV(32) LV(48) LV(64) LV(96) LV(512) LV(544)
 #undef LV
   } else if (algo == MSCCLPP_AMD_ALGO_ALLPAIR) {
     ll8Defaults(nranks, bytes, nblocks, nthreads);
     const LL8Geom g = ll8Geometry(bytes, kF16);
     if (views[0].scratchBytes < ll8ScratchRequired(nranks, bytes, kF16)) return 5;
-#define LV(VV) if (variant == VV) launchLL8T<kF16, kSum, kMaxRanks, VV>(vw, nviews, g, nranks, nblocks, nthreads, budget, s);
+    auto go = [&](auto kern) { return launchResident(kern, kern, nblocks, nviews, nthreads, s, vw, g, nranks, budget); };
+#define LV(VV) if (variant == VV) return go(allreduceLL8Kernel<kF16, kSum, kMaxRanks, VV>);
     LV(0) LV(4) LV(8) LV(12) LV(32)
 #undef LV
   } else {
     return 4;
   }
-  if (g_ll_launch_status) return g_ll_launch_status;
-  return hipGetLastError() == hipSuccess ? 0 : 1;
+  return hipGetLastError() == hipSuccess ? 0 : 1;  // no such variant: nothing launched
 }
 #endif

@@ -24,10 +24,11 @@
 //    (1, 2, 4, 8 bytes) dividing both addresses -- correct, not fast.  Tails move byte by byte: no
 //    byte outside [dstOff, dstOff + len) is written and none outside the source segment is read.
 #include <mutex>
+#include <type_traits>
 
-#include "common.hpp"
 #include "copy_range.hpp"
 #include "handshake.hpp"
+#include "launch.hpp"
 
 namespace mscclpp_amd {
 
@@ -79,7 +80,7 @@ __global__ void __launch_bounds__(512) alltoallKernel(A2AArgs<NV> a) {
   for (int s = 0; s < n; ++s) {
     const int p = (int)(((uint32_t)(rank + 1 + s) + b) % (uint32_t)n);
     const A2ASeg seg = a.segs.at(vi, p);
-    const uint64_t blk = ((seg.len + nb - 1) / nb + 15) & ~15ull;
+    const uint64_t blk = blockBytes(seg.len, nb);
     const uint64_t bOff = (uint64_t)b * blk;
     if (bOff >= seg.len) continue;
     const uint64_t len = seg.len - bOff < blk ? seg.len - bOff : blk;
@@ -97,8 +98,6 @@ __global__ void __launch_bounds__(512) alltoallKernel(A2AArgs<NV> a) {
 __global__ void alltoallTableKernel(A2ATableArg t, A2ASeg* dst) {
   if (threadIdx.x < kMaxRanks * kMaxRanks) dst[threadIdx.x] = t.s[threadIdx.x];
 }
-
-constexpr uint64_t kBlkOffsetLimit = 0xFFFFFFFFull - 64;  // as launchBroadcast: one descriptor per workgroup range
 
 // 256 KiB of the busiest rank's receive bytes per workgroup, 8..128 workgroups.  Every rank of a
 // collective must launch the same grid (workgroup b hand-shakes with the peers' workgroup b), so a
@@ -140,36 +139,26 @@ int launchAllToAll(const mscclppAmdRankView* views, int nviews, int nranks, cons
     }
     nblocks = alltoallDefaultBlocks(most);
   }
-  if (nthreads <= 0) nthreads = 512;
-  if (nblocks > kMaxChannels || nthreads > 512 || nthreads % 64 || nthreads < 64) return 4;
+  if (!launchShapeOk(nblocks, kMaxChannels, nthreads)) return 4;
   for (int i = 0; i < nviews * nranks; ++i)
-    if (((segs[i].len + nblocks - 1) / nblocks + 15) / 16 * 16 > kBlkOffsetLimit) return 5;
-  if (nviews == 1) {
-    A2AArgs<1> a{};
-    a.views.v[0] = views[0];
-    for (int p = 0; p < nranks; ++p) a.segs.s[p] = segs[p];
+    if (blockBytes(segs[i].len, (uint32_t)nblocks) > kBlkOffsetLimit) return 5;
+  return launchViews(alltoallKernel<1, 4>, alltoallKernel<kMaxRanks, 4>, views, nviews, nblocks, nthreads, s, [&](auto& a) {
     a.budget = budget;
     a.trace = g_mscclppAmdTrace;
     a.nranks = nranks;
-    if (!grid_coresident(alltoallKernel<1, 4>, nthreads, nblocks)) return 5;
-    hipLaunchKernelGGL((alltoallKernel<1, 4>), dim3(nblocks), dim3(nthreads), 0, s, a);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
-  }
-  if (!grid_coresident(alltoallKernel<kMaxRanks, 4>, nthreads, (long)nblocks * nviews)) return 5;
-  A2ATableArg t{};
-  for (int i = 0; i < nviews; ++i)
-    for (int p = 0; p < nranks; ++p) t.s[i * kMaxRanks + p] = segs[i * nranks + p];
-  A2ASeg* slot = nextTableSlot();
-  if (!slot) return 1;
-  hipLaunchKernelGGL(alltoallTableKernel, dim3(1), dim3(64), 0, s, t, slot);
-  A2AArgs<kMaxRanks> a{};
-  for (int i = 0; i < nviews; ++i) a.views.v[i] = views[i];
-  a.segs.tab = slot;
-  a.budget = budget;
-  a.trace = g_mscclppAmdTrace;
-  a.nranks = nranks;
-  hipLaunchKernelGGL((alltoallKernel<kMaxRanks, 4>), dim3(nblocks, nviews), dim3(nthreads), 0, s, a);
-  return hipGetLastError() == hipSuccess ? 0 : 1;
+    if constexpr (std::is_same_v<decltype(a.segs), A2ASegs<1>>) {
+      for (int p = 0; p < nranks; ++p) a.segs.s[p] = segs[p];
+    } else {  // the table of every view goes through a device slot, filled on the stream right before the kernel
+      A2ATableArg t{};
+      for (int i = 0; i < nviews; ++i)
+        for (int p = 0; p < nranks; ++p) t.s[i * kMaxRanks + p] = segs[i * nranks + p];
+      A2ASeg* slot = nextTableSlot();
+      if (!slot) return 1;
+      hipLaunchKernelGGL(alltoallTableKernel, dim3(1), dim3(64), 0, s, t, slot);
+      a.segs.tab = slot;
+    }
+    return 0;
+  });
 }
 
 }  // namespace mscclpp_amd

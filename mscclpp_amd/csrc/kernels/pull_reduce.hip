@@ -34,8 +34,8 @@
 //    buffer's extent is read.  Pointers need their element's alignment only and the misalignment
 //    may differ between ranks and between send and receive: one descriptor per buffer, rebased to
 //    the workgroup's range (64-bit), with 32-bit offsets inside it.
-#include "common.hpp"
 #include "handshake.hpp"
+#include "launch.hpp"
 #include "mscclpp_amd/pull_reduce_device.hpp"
 
 namespace mscclpp_amd {
@@ -47,18 +47,13 @@ namespace mscclpp_amd {
 // workgroups needs to be resident at once.
 constexpr int kPullReduceUnits = 2;
 
-// ceil(len / nblocks) rounded up to whole 16-byte units, of the largest range of the collective.
-__host__ __device__ inline uint64_t pullReduceBlockBytes(uint64_t maxLen, uint32_t nblocks) {
-  return ((maxLen + nblocks - 1) / nblocks + 15) & ~15ull;
-}
-
 template <int NV>
 struct PullReduceArgs {
   Views<NV> views;
   uint64_t srcOff[kMaxRanks];  // rank q reduces [srcOff[q], + len[q]) of every send buffer
   uint64_t dstOff[kMaxRanks];  // into its receive buffer at dstOff[q]
   uint64_t len[kMaxRanks];
-  uint64_t blk;     // pullReduceBlockBytes(max len, gridDim.x)
+  uint64_t blk;     // blockBytes(max len, gridDim.x): of the largest range of the collective
   uint64_t budget;
   uint64_t* trace;  // phase stamps: 0 start, 1 entry handshake done, 2 reduced, 3 gathered, 4 end
   float invN;       // 1.0f / (float)nranks, computed once by the host (AVG of the float types)
@@ -158,8 +153,6 @@ __global__ void __launch_bounds__(512) pullReduceKernel(PullReduceArgs<NV> a) {
   trace_stamp(a.trace, 4);
 }
 
-static constexpr uint64_t kPullBlkOffsetLimit = 0xFFFFFFFFull - 64;  // as reduce.hip: one descriptor per workgroup range
-
 int reduceDefaultBlocks(uint64_t bytes);  // reduce.hip
 
 // The default grid is a function of (collective, bytes) alone, so every rank derives the same one;
@@ -202,50 +195,38 @@ uint64_t pullReduceGeometry(int coll, int nranks, uint64_t bytes, int root, uint
   return most;
 }
 
-static thread_local int g_pull_reduce_status = 0;
-
 template <int DT, int OP>
-static void launchPullReduceT(const mscclppAmdRankView* views, int nviews, int nranks, int coll, uint64_t bytes, int root,
-                              uint64_t blk, int nblocks, int nthreads, uint64_t budget, hipStream_t s) {
-  auto go = [&](auto kern, auto args) {
-    for (int i = 0; i < nviews; ++i) args.views.v[i] = views[i];
-    pullReduceGeometry(coll, nranks, bytes, root, args.srcOff, args.dstOff, args.len);
-    args.blk = blk;
-    args.budget = budget;
-    args.trace = g_mscclppAmdTrace;
-    args.invN = 1.0f / (float)nranks;
-    args.nranks = nranks;
-    args.gather = coll == MSCCLPP_AMD_PULL_ALLREDUCE;
-    if (!grid_coresident(kern, nthreads, (long)nblocks * nviews)) {
-      g_pull_reduce_status = 5;  // ncclInvalidUsage: the handshakes of a non-resident grid would deadlock
-      return;
-    }
-    hipLaunchKernelGGL(kern, dim3(nblocks, nviews), dim3(nthreads), 0, s, args);
-  };
-  if (nviews == 1)
-    go(pullReduceKernel<DT, OP, 1, kPullReduceUnits>, PullReduceArgs<1>{});
-  else
-    go(pullReduceKernel<DT, OP, kMaxRanks, kPullReduceUnits>, PullReduceArgs<kMaxRanks>{});
+static int launchPullReduceT(const mscclppAmdRankView* views, int nviews, int nranks, int coll, uint64_t bytes, int root,
+                             uint64_t blk, int nblocks, int nthreads, uint64_t budget, hipStream_t s) {
+  return launchViews(pullReduceKernel<DT, OP, 1, kPullReduceUnits>, pullReduceKernel<DT, OP, kMaxRanks, kPullReduceUnits>,
+                     views, nviews, nblocks, nthreads, s, [&](auto& args) {
+                       pullReduceGeometry(coll, nranks, bytes, root, args.srcOff, args.dstOff, args.len);
+                       args.blk = blk;
+                       args.budget = budget;
+                       args.trace = g_mscclppAmdTrace;
+                       args.invN = 1.0f / (float)nranks;
+                       args.nranks = nranks;
+                       args.gather = coll == MSCCLPP_AMD_PULL_ALLREDUCE;
+                       return 0;
+                     });
 }
 
 #define MSCCLPP_AMD_PULL_CASE2(DT, ...)                                            \
-  case DT * 4 + kPullMax: launchPullReduceT<DT, kPullMax>(__VA_ARGS__); break;     \
-  case DT * 4 + kPullAvg: launchPullReduceT<DT, kPullAvg>(__VA_ARGS__); break;
+  case DT * 4 + kPullMax: return launchPullReduceT<DT, kPullMax>(__VA_ARGS__);     \
+  case DT * 4 + kPullAvg: return launchPullReduceT<DT, kPullAvg>(__VA_ARGS__);
 
 int launchPullReduce(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes, int dtype, int op,
                      int root, int nblocks, int nthreads, uint64_t budget, hipStream_t s) {
   if (coll < MSCCLPP_AMD_PULL_REDUCE || coll > MSCCLPP_AMD_PULL_ALLREDUCE) return 4;
   if (nblocks <= 0) nblocks = pullReduceDefaultBlocks(coll, bytes);
-  if (nthreads <= 0) nthreads = 512;
-  if (nblocks > kMaxChannels || nthreads > 512 || nthreads % 64 || nthreads < 64) return 4;
+  if (!launchShapeOk(nblocks, kMaxChannels, nthreads)) return 4;
   if (nranks < 2 || nranks > kMaxRanks || bytes == 0) return 4;
   if (coll == MSCCLPP_AMD_PULL_REDUCE && (root < 0 || root >= nranks)) return 4;
   if ((op != kPullMax && op != kPullAvg) || !pull_reduce_carries(dtype) || bytes % (size_t)elem_bytes(dtype)) return 4;
   uint64_t srcOff[kMaxRanks], dstOff[kMaxRanks], len[kMaxRanks];
   const uint64_t most = pullReduceGeometry(coll, nranks, bytes, root, srcOff, dstOff, len);
-  const uint64_t blk = pullReduceBlockBytes(most, (uint32_t)nblocks);
-  if (blk > kPullBlkOffsetLimit) return 5;  // more workgroups needed: one workgroup's range is one descriptor
-  g_pull_reduce_status = 0;
+  const uint64_t blk = blockBytes(most, (uint32_t)nblocks);
+  if (blk > kBlkOffsetLimit) return 5;  // more workgroups needed: one workgroup's range is one descriptor
   switch (dtype * 4 + op) {
     MSCCLPP_AMD_PULL_CASE2(kF16, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)
     MSCCLPP_AMD_PULL_CASE2(kBF16, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)
@@ -257,8 +238,6 @@ int launchPullReduce(const mscclppAmdRankView* views, int nviews, int nranks, in
     MSCCLPP_AMD_PULL_CASE2(kU8, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)
     default: return 4;
   }
-  if (g_pull_reduce_status) return g_pull_reduce_status;
-  return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
 }  // namespace mscclpp_amd

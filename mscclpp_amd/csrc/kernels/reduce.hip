@@ -13,7 +13,7 @@
 //    stream work on its receive buffer is over.  Exit: the root has finished reading, so a non-root
 //    rank may overwrite its send buffer in its next stream operation.  Non-root workgroups do nothing
 //    between the two handshakes: they read and write no user memory.
-//  * On the root workgroup b owns [b * blk, (b + 1) * blk) of the message (reduceBlockBytes).  Per
+//  * On the root workgroup b owns [b * blk, (b + 1) * blk) of the message (blockBytes).  Per
 //    16-byte unit: the own unit by a local load, the same unit of every peer by system-scope loads,
 //    all issued before any arithmetic; U units per lane are in flight (the loads of all U units come
 //    first, then the reduces and stores).  A lane stores only units it has itself loaded, so the
@@ -25,8 +25,8 @@
 //    `bytes` is read.  Pointers need their element's alignment only, and the misalignment may differ
 //    between ranks and between a rank's send and receive buffers: each buffer is addressed through a
 //    descriptor of its own, rebased to the workgroup's range (64-bit), with 32-bit offsets inside it.
-#include "common.hpp"
 #include "handshake.hpp"
+#include "launch.hpp"
 
 namespace mscclpp_amd {
 
@@ -41,17 +41,11 @@ namespace mscclpp_amd {
 // once; U = 4 would leave one (8 x 32).
 constexpr int kReduceUnits = 2;
 
-// The one statement of how a message is split over workgroups, for the launcher's limit check and
-// the kernel (which receives the value): ceil(bytes / nblocks) rounded up to whole 16-byte units.
-__host__ __device__ inline uint64_t reduceBlockBytes(uint64_t bytes, uint32_t nblocks) {
-  return ((bytes + nblocks - 1) / nblocks + 15) & ~15ull;
-}
-
 template <int NV>
 struct ReduceArgs {
   Views<NV> views;
   uint64_t bytes;
-  uint64_t blk;     // reduceBlockBytes(bytes, gridDim.x)
+  uint64_t blk;     // blockBytes(bytes, gridDim.x)
   uint64_t budget;
   uint64_t* trace;  // phase stamps: 0 start, 1 entry handshake done, 2 result stored, 3 end
   int nranks;
@@ -118,8 +112,6 @@ __global__ void __launch_bounds__(512) reduceKernel(ReduceArgs<NV> a) {
   trace_stamp(a.trace, 3);
 }
 
-constexpr uint64_t kBlkOffsetLimit = 0xFFFFFFFFull - 64;  // as launchBroadcast: one descriptor per workgroup range
-
 // 32 KiB of the message per workgroup, 8..64 workgroups.  Broadcast and AllToAll take 256 KiB per
 // workgroup, 8..128, but there every rank's workgroups move data; here only the root's do, and the
 // in-process sweep (8, 32 and 64 workgroups are the fastest 512-lane grids at 64 KiB,
@@ -132,46 +124,32 @@ int reduceDefaultBlocks(uint64_t bytes) {
   return (int)(want < 8 ? 8 : want > 64 ? 64 : want);
 }
 
-static thread_local int g_reduce_status = 0;
-
 template <int DT, int OP>
-static void launchReduceT(const mscclppAmdRankView* views, int nviews, int nranks, uint64_t bytes, uint64_t blk, int root,
-                          int nblocks, int nthreads, uint64_t budget, hipStream_t s) {
-  auto go = [&](auto kern, auto args) {
-    for (int i = 0; i < nviews; ++i) args.views.v[i] = views[i];
-    args.bytes = bytes;
-    args.blk = blk;
-    args.budget = budget;
-    args.trace = g_mscclppAmdTrace;
-    args.nranks = nranks;
-    args.root = root;
-    if (!grid_coresident(kern, nthreads, (long)nblocks * nviews)) {
-      g_reduce_status = 5;  // ncclInvalidUsage: the handshakes of a non-resident grid would deadlock
-      return;
-    }
-    hipLaunchKernelGGL(kern, dim3(nblocks, nviews), dim3(nthreads), 0, s, args);
-  };
-  if (nviews == 1)
-    go(reduceKernel<DT, OP, 1, kReduceUnits>, ReduceArgs<1>{});
-  else
-    go(reduceKernel<DT, OP, kMaxRanks, kReduceUnits>, ReduceArgs<kMaxRanks>{});
+static int launchReduceT(const mscclppAmdRankView* views, int nviews, int nranks, uint64_t bytes, uint64_t blk, int root,
+                         int nblocks, int nthreads, uint64_t budget, hipStream_t s) {
+  return launchViews(reduceKernel<DT, OP, 1, kReduceUnits>, reduceKernel<DT, OP, kMaxRanks, kReduceUnits>, views, nviews,
+                     nblocks, nthreads, s, [&](auto& args) {
+                       args.bytes = bytes;
+                       args.blk = blk;
+                       args.budget = budget;
+                       args.trace = g_mscclppAmdTrace;
+                       args.nranks = nranks;
+                       args.root = root;
+                       return 0;
+                     });
 }
 
 int launchReduce(const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes, int dtype, int op, int root,
                  int nblocks, int nthreads, uint64_t budget, hipStream_t s) {
   if (nblocks <= 0) nblocks = reduceDefaultBlocks(bytes);
-  if (nthreads <= 0) nthreads = 512;
-  if (nblocks > kMaxChannels || nthreads > 512 || nthreads % 64 || nthreads < 64) return 4;
+  if (!launchShapeOk(nblocks, kMaxChannels, nthreads)) return 4;
   if (root < 0 || root >= nranks || bytes == 0) return 4;
   if (dtype < 0 || dtype >= MSCCLPP_AMD_NUM_DTYPES || (op != kSum && op != kMin) || bytes % (size_t)elem_bytes(dtype))
     return 4;
-  const uint64_t blk = reduceBlockBytes(bytes, (uint32_t)nblocks);
+  const uint64_t blk = blockBytes(bytes, (uint32_t)nblocks);
   if (blk > kBlkOffsetLimit) return 5;  // more workgroups needed: one workgroup's range is one descriptor
-  g_reduce_status = 0;
   MSCCLPP_AMD_DISPATCH_ALL(dtype, op, launchReduceT, views, nviews, nranks, (uint64_t)bytes, blk, root, nblocks, nthreads,
                            budget, s);
-  if (g_reduce_status) return g_reduce_status;
-  return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
 }  // namespace mscclpp_amd

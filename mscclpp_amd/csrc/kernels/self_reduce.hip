@@ -256,8 +256,8 @@ static void launchSelfReduceShape(const void* x, const void* y, void* pkts, void
 }
 
 template <int DT, int OP>
-static void launchSelfReduce(const void* x, const void* y, void* pkts, void* out, uint64_t bytes, uint32_t* flags,
-                             int nblocks, uint64_t budget, uint32_t* err, hipStream_t stream) {
+static int launchSelfReduce(const void* x, const void* y, void* pkts, void* out, uint64_t bytes, uint32_t* flags,
+                            int nblocks, uint64_t budget, uint32_t* err, hipStream_t stream) {
   const SelfReduceShape sh = selfReduceShape(bytes, nblocks);
   // wave w of a workgroup consumes what wave w ^ 1 of the same workgroup packed (PMASK 0)
   if (sh.waves == 8)
@@ -275,6 +275,7 @@ static void launchSelfReduce(const void* x, const void* y, void* pkts, void* out
   else  // a caller's grid with more workgroups than tiles
     launchSelfReduceShape<DT, OP, 4, 1, 0, false, kNonTemporal, 0>(x, y, pkts, out, bytes, flags, sh.nblocks, budget,
                                                                    err, nullptr, stream);
+  return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
 // Streaming copy (read S, write S) used by the benchmark to measure the achievable HBM ceiling on
@@ -578,5 +579,4 @@ extern "C" int mscclppAmdSelfReduceLL16(const void* x, const void* y, void* pkts
   // 1024 workgroups = 4 per CU (16 KiB LDS each), all resident, so every partner pair is co-resident
   if (nblocks > 1024) return 4;
   MSCCLPP_AMD_DISPATCH_ALL(dtype, op, launchSelfReduce, x, y, pkts, out, (uint64_t)bytes, flags, nblocks, budgetTicks, err, stream);
-  return hipGetLastError() == hipSuccess ? 0 : 1;
 }

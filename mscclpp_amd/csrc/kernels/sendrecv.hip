@@ -34,9 +34,9 @@
 // collectives that share them.  Several operations of one pair and direction count up on the
 // channels they share: the k-th send meets the k-th receive.  The grid is the largest nb of the
 // table; a workgroup skips the operations with nb(op) <= b.
-#include "common.hpp"
 #include "copy_range.hpp"
 #include "handshake.hpp"
+#include "launch.hpp"
 
 namespace mscclpp_amd {
 
@@ -75,9 +75,6 @@ __host__ __device__ inline uint32_t sendrecvBlocks(uint64_t bytes, int force) {
   if (force > 0) return (uint32_t)force;
   const uint64_t want = (bytes + kSRBytesPerBlock - 1) / kSRBytesPerBlock;
   return (uint32_t)(want < 1 ? 1 : want > kSRDefaultMaxBlocks ? kSRDefaultMaxBlocks : want);
-}
-__host__ __device__ inline uint64_t sendrecvBlockBytes(uint64_t bytes, uint32_t nb) {
-  return ((bytes + nb - 1) / nb + 15) & ~15ull;
 }
 __host__ __device__ inline uint32_t sendrecvChannelBase(int src, int dst) { return src < dst ? 0u : (uint32_t)kSRDirChannels; }
 
@@ -132,7 +129,7 @@ __global__ void __launch_bounds__(512) sendrecvKernel(SRArgs<NV> a) {
     const uint32_t rch = sendrecvChannelBase(op.src, op.dst) + b;
     if (tid == 0) token_wait(v.tokens, v.expected, v.err, op.src, rank, rch, a.budget);
     __syncthreads();
-    const uint64_t blk = sendrecvBlockBytes(op.bytes, nb), bOff = (uint64_t)b * blk;
+    const uint64_t blk = blockBytes(op.bytes, nb), bOff = (uint64_t)b * blk;
     if (bOff < op.bytes) {
       const uint64_t len = op.bytes - bOff < blk ? op.bytes - bOff : blk;  // <= kBlkOffsetLimit
       copy_range<kSystem, U>((const uint8_t*)op.send + bOff, (uint8_t*)op.recv + bOff, len, tid, T);
@@ -146,21 +143,18 @@ __global__ void __launch_bounds__(512) sendrecvKernel(SRArgs<NV> a) {
   trace_stamp(a.trace, 3);
 }
 
-constexpr uint64_t kBlkOffsetLimit = 0xFFFFFFFFull - 64;  // as launchAllToAll: one descriptor per workgroup range
-
 int sendrecvDefaultBlocks(uint64_t bytes) { return (int)sendrecvBlocks(bytes, 0); }
 
 // Every argument was checked by the caller (mscclppAmdSendRecvLaunch) except the launch shape and
 // the sizes; nothing here touches the device before those checks have passed.
 int launchSendRecv(const mscclppAmdRankView* views, int nviews, int nranks, const SROp* ops, int nops, int nblocks,
                    int nthreads, uint64_t budget, hipStream_t s) {
-  if (nthreads <= 0) nthreads = 512;
-  if (nblocks > kSRDirChannels || nthreads > 512 || nthreads % 64 || nthreads < 64) return 4;
+  if (!launchShapeOk(nblocks, kSRDirChannels, nthreads)) return 4;
   if (nops < 1 || nops > kSRMaxOps) return 4;
   uint32_t grid = 0;
   for (int i = 0; i < nops; ++i) {
     const uint32_t nb = sendrecvBlocks(ops[i].bytes, nblocks);
-    if (sendrecvBlockBytes(ops[i].bytes, nb) > kBlkOffsetLimit) return 5;  // more workgroups carry it
+    if (blockBytes(ops[i].bytes, nb) > kBlkOffsetLimit) return 5;  // more workgroups carry it
     grid = nb > grid ? nb : grid;
   }
   auto go = [&](auto kern, auto args) {
@@ -177,9 +171,7 @@ int launchSendRecv(const mscclppAmdRankView* views, int nviews, int nranks, cons
     args.trace = g_mscclppAmdTrace;
     args.nops = nops;
     args.force = nblocks > 0 ? nblocks : 0;
-    if (!grid_coresident(kern, nthreads, (long)grid * nviews)) return 5;  // the waits of a non-resident grid would deadlock
-    hipLaunchKernelGGL(kern, dim3(grid, nviews), dim3(nthreads), 0, s, args);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return launchResident(kern, kern, (int)grid, nviews, nthreads, s, args);
   };
   if (nviews == 1) return go(sendrecvKernel<1, kSendRecvUnits>, SRArgs<1>{});
   return go(sendrecvKernel<kMaxRanks, kSendRecvUnits>, SRArgs<kMaxRanks>{});
