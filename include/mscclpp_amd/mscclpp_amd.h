@@ -57,6 +57,11 @@ enum { MSCCLPP_AMD_SUM = 0, MSCCLPP_AMD_MIN = 1 };
 /* ncclMax / ncclAvg: accepted ONLY by mscclppAmdPullReduceLaunch (and through it by ncclAllReduce /
  * ncclReduceScatter / ncclReduce); every other entry point keeps the op range SUM .. MIN. */
 enum { MSCCLPP_AMD_MAX = 2, MSCCLPP_AMD_AVG = 3 };
+/* int64 / uint64 / int8 (ncclInt64 / ncclUint64 / ncclInt8): likewise accepted ONLY by
+ * mscclppAmdPullReduceLaunch (and through it by ncclAllReduce / ncclReduceScatter / ncclReduce), there
+ * with all of SUM, MIN, MAX and AVG.  They lie beyond MSCCLPP_AMD_NUM_DTYPES, which keeps bounding the
+ * types of every other entry point. */
+enum { MSCCLPP_AMD_I64 = 16, MSCCLPP_AMD_U64 = 17, MSCCLPP_AMD_I8 = 18 };
 /* the collectives of mscclppAmdPullReduceLaunch */
 enum { MSCCLPP_AMD_PULL_REDUCE = 0, MSCCLPP_AMD_PULL_REDUCE_SCATTER = 1, MSCCLPP_AMD_PULL_ALLREDUCE = 2 };
 
@@ -211,7 +216,8 @@ int mscclppAmdAllToAllLaunch(const mscclppAmdRankView* views, int nviews, int nr
  * workgroup's range exceeds 4 GiB (more workgroups carry it), or the grid cannot be resident at once. */
 int mscclppAmdReduceLaunch(const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes, int dtype, int op,
                            int root, int nblocks, int nthreads, uint64_t budgetTicks, void* stream);
-/* ncclMax / ncclAvg of Reduce, ReduceScatter and AllReduce by one zero-copy pull-reduce kernel
+/* ncclMax / ncclAvg of Reduce, ReduceScatter and AllReduce, and all four operations of int64 /
+ * uint64 / int8, by one zero-copy pull-reduce kernel
  * (kernels/pull_reduce.hip; arithmetic: pull_reduce_device.hpp).  Operands are taken in rank order
  * 0 .. n - 1 whichever rank reduces an element, so the three collectives give the same bits for
  * the same inputs.  coll MSCCLPP_AMD_PULL_REDUCE: `bytes` of every input reduced into the root's
@@ -221,12 +227,14 @@ int mscclppAmdReduceLaunch(const mscclppAmdRankView* views, int nviews, int nran
  * slices out of peerOutput[q].  Views as for mscclppAmdReduceLaunch, plus peerOutput[q] for
  * AllReduce.  In place is carried as input == output (Reduce on the root, AllReduce) and output ==
  * input + rank * bytes (ReduceScatter); the caller rules out any other overlap.  op: MSCCLPP_AMD_MAX
- * or MSCCLPP_AMD_AVG; dtype: F16, BF16, F32, I32, U32, U8, E4M3, E5M2; pointers need the element's
- * alignment only.  root is read for Reduce only.  nblocks <= 0: mscclppAmdPullReduceDefaultBlocks,
- * a function of (coll, bytes) alone; every rank of one collective must launch the same nblocks.
- * 4 (nothing is launched, no device is touched): SUM / MIN (they have their own kernels), any
- * other dtype code, a byte count of 0 or one that splits an element, a bad root, coll or launch
- * shape, null fields; 5: a workgroup's range exceeds 4 GiB (more workgroups carry it), or the grid
+ * or MSCCLPP_AMD_AVG with dtype F16, BF16, F32, I32, U32, U8, E4M3, E5M2; MSCCLPP_AMD_SUM, _MIN, _MAX
+ * or _AVG with dtype I64, U64, I8 (wrapping sums, signed / unsigned compares, the exact sum divided
+ * by nranks toward zero); pointers need the element's alignment only (8 bytes for I64 / U64).  root
+ * is read for Reduce only.  nblocks <= 0: mscclppAmdPullReduceDefaultBlocks, a function of (coll,
+ * bytes) alone; every rank of one collective must launch the same nblocks.  4 (nothing is launched,
+ * no device is touched): SUM / MIN of the eight types that have their own kernels for them, any
+ * other op or dtype code, a byte count of 0 or one that splits an element, a bad root, coll or
+ * launch shape, null fields; 5: a workgroup's range exceeds 4 GiB (more workgroups carry it), or the grid
  * cannot be resident at once. */
 int mscclppAmdPullReduceLaunch(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes, int dtype,
                                int op, int root, int nblocks, int nthreads, uint64_t budgetTicks, void* stream);

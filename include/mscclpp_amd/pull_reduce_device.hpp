@@ -1,6 +1,7 @@
-// ncclMax / ncclAvg arithmetic of the pull-reduce kernel (kernels/pull_reduce.hip), over packed
-// 32-bit words.  The reference carries SUM and MIN only (reduce_device.hpp restates those bit for
-// bit), so these two are defined here, not restated:
+// Arithmetic of the pull-reduce kernel (kernels/pull_reduce.hip), over packed 32-bit words: ncclMax /
+// ncclAvg of the eight element types the SUM / MIN kernels carry, and all four operations of int64,
+// uint64 and int8.  The reference carries SUM and MIN of its own types only (reduce_device.hpp
+// restates those bit for bit), so what follows is defined here, not restated:
 //
 //  * operands are taken in RANK order 0, 1, ..., n - 1 on whichever rank computes the element, so
 //    Reduce, ReduceScatter and AllReduce of the same inputs give the same bits;
@@ -14,7 +15,18 @@
 //    element type: fp32 as is, (_Float16)r, (__bf16)r (RNE, none of the SUM path's clipping),
 //    fp8x4_encode (saturating, RNE);
 //  * AVG, integers: the exact sum (int64 / uint64 / uint32 for int32 / uint32 / uint8) divided by n,
-//    truncating toward zero.
+//    truncating toward zero;
+//  * int64 / uint64 / int8 (kI64, kU64, kI8; SUM and MIN too, which the other types take to their own
+//    kernels).  Every one of these operations is exact, so the rank order changes no bit:
+//      SUM: two's-complement wrap at the element width (the reference's rule for int32 / uint8); an
+//           int8 sum is per byte, no carry crosses a byte boundary;
+//      MIN / MAX: signed compare for int64 and int8, unsigned for uint64, over all 64 bits;
+//      AVG: the EXACT sum divided by n, truncating toward zero -- not the wrapped sum divided by n.
+//           int8: the sum of 8 values fits 16 bits.  64-bit: the sum is kept as a 96-bit two's-
+//           complement value {hi, lo} (it needs 67 bits), its magnitude M = hi * 2^64 + lo has
+//           hi < n, and with c1 = floor(2^64 / n), c2 = 2^64 mod n (constants per n)
+//           M / n = hi * c1 + lo / n + (hi * c2 + lo % n) / n: one 64-bit divide by a constant per
+//           element; the sign is put back afterwards.
 #pragma once
 
 #include "reduce_device.hpp"
@@ -25,10 +37,23 @@ namespace mscclpp_amd {
 // kernels of ROp keep their range.
 enum PullOp : int { kPullMax = 2, kPullAvg = 3 };
 
-// The reduce types the path carries: the eight element types, accumulated as defined above.
+// int64 / uint64 / int8: carried by this path alone, with kSum and kMin as well.
+__host__ __device__ constexpr bool pull_only_type(int dt) { return dt == kI64 || dt == kU64 || dt == kI8; }
+
+// The reduce types the path carries: the eight element types and the three above, accumulated as
+// defined above.
 __host__ __device__ constexpr bool pull_reduce_carries(int dt) {
-  return dt == kF16 || dt == kBF16 || dt == kF32 || dt == kI32 || dt == kU32 || dt == kE4M3 || dt == kE5M2 || dt == kU8;
+  return dt == kF16 || dt == kBF16 || dt == kF32 || dt == kI32 || dt == kU32 || dt == kE4M3 || dt == kE5M2 ||
+         dt == kU8 || pull_only_type(dt);
 }
+// MAX / AVG for every carried type; SUM / MIN exactly for the three types that have no other kernel.
+__host__ __device__ constexpr bool pull_reduce_takes(int dt, int op) {
+  return pull_reduce_carries(dt) &&
+         (op == kPullMax || op == kPullAvg || ((op == kSum || op == kMin) && pull_only_type(dt)));
+}
+// 32-bit words an accumulator consumes at a time: 2 for the 64-bit types (first / next take and
+// word() returns a uint64_t), 1 for every other type.
+__host__ __device__ constexpr int pull_acc_words(int dt) { return dt == kI64 || dt == kU64 ? 2 : 1; }
 
 __device__ __forceinline__ bool max_takes(float acc, float x) { return acc != acc || x > acc; }
 
@@ -193,6 +218,151 @@ struct PullAcc<kU8, kPullAvg> {
   __device__ __forceinline__ uint32_t word(int n, float) const {
     return div_ranks<uint32_t>(even & 0xffffu, n) | (div_ranks<uint32_t>(odd & 0xffffu, n) << 8) |
            (div_ranks<uint32_t>(even >> 16, n) << 16) | (div_ranks<uint32_t>(odd >> 16, n) << 24);
+  }
+};
+
+// ---- int8: SUM / MIN / MAX / AVG per byte ---------------------------------------------------------
+template <int OP>
+struct PullAccI8 {
+  uint32_t a;
+  __device__ __forceinline__ void first(uint32_t w) { a = w; }
+  __device__ __forceinline__ void next(uint32_t w) {
+    if constexpr (OP == kSum) {
+      // the low seven bits of every byte add without reaching the next byte; the top bits add by xor
+      a = ((a & 0x7f7f7f7fu) + (w & 0x7f7f7f7fu)) ^ ((a ^ w) & 0x80808080u);
+    } else {
+      uint32_t r = 0;
+#pragma unroll
+      for (int k = 0; k < 32; k += 8) {
+        const int32_t x = (int8_t)(a >> k), y = (int8_t)(w >> k);
+        const int32_t t = OP == kMin ? (y < x ? y : x) : (y > x ? y : x);
+        r |= ((uint32_t)t & 0xffu) << k;
+      }
+      a = r;
+    }
+  }
+  __device__ __forceinline__ uint32_t word(int, float) const { return a; }
+};
+template <>
+struct PullAcc<kI8, kSum> : PullAccI8<kSum> {};
+template <>
+struct PullAcc<kI8, kMin> : PullAccI8<kMin> {};
+template <>
+struct PullAcc<kI8, kPullMax> : PullAccI8<kPullMax> {};
+
+template <>
+struct PullAcc<kI8, kPullAvg> {
+  // two 16-bit sums each (bytes 0 and 2, bytes 1 and 3) of the bytes biased by 128 (x ^ 0x80 = x + 128
+  // as an unsigned byte): at most 8 x 255, so no field reaches its neighbour
+  uint32_t even, odd;
+  __device__ __forceinline__ void first(uint32_t w) {
+    w ^= 0x80808080u;
+    even = w & 0x00ff00ffu;
+    odd = (w >> 8) & 0x00ff00ffu;
+  }
+  __device__ __forceinline__ void next(uint32_t w) {
+    w ^= 0x80808080u;
+    even += w & 0x00ff00ffu;
+    odd += (w >> 8) & 0x00ff00ffu;
+  }
+  static __device__ __forceinline__ uint32_t byte_of(uint32_t biased, int n) {
+    return (uint32_t)div_ranks<int32_t>((int32_t)biased - 128 * n, n) & 0xffu;  // signed: toward zero
+  }
+  __device__ __forceinline__ uint32_t word(int n, float) const {
+    return byte_of(even & 0xffffu, n) | (byte_of(odd & 0xffffu, n) << 8) | (byte_of(even >> 16, n) << 16) |
+           (byte_of(odd >> 16, n) << 24);
+  }
+};
+
+// ---- int64 / uint64: one element = two words ------------------------------------------------------
+template <int DT, int OP>
+struct PullAcc64 {
+  uint64_t a;
+  __device__ __forceinline__ void first(uint64_t x) { a = x; }
+  __device__ __forceinline__ void next(uint64_t x) {
+    if constexpr (OP == kSum) {
+      a += x;
+    } else if constexpr (DT == kI64) {
+      const bool take = OP == kMin ? (int64_t)x < (int64_t)a : (int64_t)x > (int64_t)a;
+      a = take ? x : a;
+    } else {
+      const bool take = OP == kMin ? x < a : x > a;
+      a = take ? x : a;
+    }
+  }
+  __device__ __forceinline__ uint64_t word(int, float) const { return a; }
+};
+template <>
+struct PullAcc<kI64, kSum> : PullAcc64<kI64, kSum> {};
+template <>
+struct PullAcc<kI64, kMin> : PullAcc64<kI64, kMin> {};
+template <>
+struct PullAcc<kI64, kPullMax> : PullAcc64<kI64, kPullMax> {};
+template <>
+struct PullAcc<kU64, kSum> : PullAcc64<kU64, kSum> {};
+template <>
+struct PullAcc<kU64, kMin> : PullAcc64<kU64, kMin> {};
+template <>
+struct PullAcc<kU64, kPullMax> : PullAcc64<kU64, kPullMax> {};
+
+// (hi * 2^64 + lo) / D for hi < D, D a rank count: see the opening comment.  The result fits 64 bits.
+// (This and the two AVG accumulators below are __host__ as well, so that a host program can compare
+// them with __int128 arithmetic.)
+template <uint32_t D>
+__host__ __device__ __forceinline__ uint64_t div96_by(uint32_t hi, uint64_t lo) {
+  constexpr uint64_t kAll = ~0ull;
+  constexpr uint64_t c1 = kAll / D + (kAll % D == D - 1 ? 1 : 0);  // floor(2^64 / D)
+  constexpr uint32_t c2 = (uint32_t)((kAll % D + 1) % D);          // 2^64 mod D
+  const uint64_t q = lo / D;
+  const uint32_t r = (uint32_t)(lo - q * D);
+  return (uint64_t)hi * c1 + q + (hi * c2 + r) / D;
+}
+__host__ __device__ __forceinline__ uint64_t div96_ranks(uint32_t hi, uint64_t lo, int n) {
+  switch (n) {
+    case 2: return div96_by<2>(hi, lo);
+    case 3: return div96_by<3>(hi, lo);
+    case 4: return div96_by<4>(hi, lo);
+    case 5: return div96_by<5>(hi, lo);
+    case 6: return div96_by<6>(hi, lo);
+    case 7: return div96_by<7>(hi, lo);
+    default: return div96_by<8>(hi, lo);
+  }
+}
+
+template <>
+struct PullAcc<kU64, kPullAvg> {
+  uint64_t lo;
+  uint32_t hi;  // carries out of lo: at most n - 1
+  __host__ __device__ __forceinline__ void first(uint64_t x) {
+    lo = x;
+    hi = 0;
+  }
+  __host__ __device__ __forceinline__ void next(uint64_t x) {
+    lo += x;
+    hi += lo < x ? 1u : 0u;
+  }
+  __host__ __device__ __forceinline__ uint64_t word(int n, float) const { return div96_ranks(hi, lo, n); }
+};
+
+template <>
+struct PullAcc<kI64, kPullAvg> {
+  uint64_t lo;
+  int32_t hi;  // {hi, lo}: the 96-bit two's-complement sum of the sign-extended operands
+  __host__ __device__ __forceinline__ void first(uint64_t x) {
+    lo = x;
+    hi = (int64_t)x < 0 ? -1 : 0;
+  }
+  __host__ __device__ __forceinline__ void next(uint64_t x) {
+    lo += x;
+    hi += ((int64_t)x < 0 ? -1 : 0) + (lo < x ? 1 : 0);
+  }
+  __host__ __device__ __forceinline__ uint64_t word(int n, float) const {
+    const bool neg = hi < 0;
+    // the magnitude: at most n * 2^63, so its high part stays below n
+    const uint64_t mlo = neg ? 0 - lo : lo;
+    const uint32_t mhi = neg ? ~(uint32_t)hi + (lo == 0 ? 1u : 0u) : (uint32_t)hi;
+    const uint64_t q = div96_ranks(mhi, mlo, n);
+    return neg ? 0 - q : q;
   }
 };
 

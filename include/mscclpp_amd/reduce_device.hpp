@@ -26,7 +26,10 @@ enum DType : int {
   kE4M3AccF16 = 7, kE5M2AccF16 = 8,  // AccumT = half
   kE4M3AccF32 = 9, kE5M2AccF32 = 10, // AccumT = float
   kU8 = 11,                          // uint8_t (Adapter<Op, uint8_t, uint8_t>, common.hpp:132-133)
-  kB15 = 12, kB15AccF16 = 13, kB15AccF32 = 14  // __fp8_e4m3b15, AccumT = T / half / float
+  kB15 = 12, kB15AccF16 = 13, kB15AccF32 = 14,  // __fp8_e4m3b15, AccumT = T / half / float
+  // int64_t / uint64_t / int8_t: the pull-reduce kernel only (pull_reduce_device.hpp); they lie
+  // beyond MSCCLPP_AMD_NUM_DTYPES, which bounds the <DT, OP> kernels pinned to the reference
+  kI64 = 16, kU64 = 17, kI8 = 18
 };
 enum ROp : int { kSum = 0, kMin = 1 };
 
@@ -34,7 +37,8 @@ __host__ __device__ constexpr bool is_fp8(int dt) { return dt >= kE4M3 && dt <= 
 __host__ __device__ constexpr bool is_b15(int dt) { return dt >= kB15 && dt <= kB15AccF32; }
 __host__ __device__ constexpr bool is_e5m2(int dt) { return dt == kE5M2 || dt == kE5M2AccF16 || dt == kE5M2AccF32; }
 __host__ __device__ constexpr int elem_bytes(int dt) {
-  return (dt == kF16 || dt == kBF16) ? 2 : ((is_fp8(dt) || is_b15(dt) || dt == kU8) ? 1 : 4);
+  return (dt == kI64 || dt == kU64) ? 8
+         : (dt == kF16 || dt == kBF16) ? 2 : ((is_fp8(dt) || is_b15(dt) || dt == kU8 || dt == kI8) ? 1 : 4);
 }
 
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));

@@ -24,6 +24,9 @@ E4M3, E5M2, E4M3_ACC_F16, E5M2_ACC_F16, E4M3_ACC_F32, E5M2_ACC_F32 = 5, 6, 7, 8,
 # uint8, and the software fp8 e4m3b15 accumulated in itself / half / float (no torch dtype: pass
 # uint8 tensors with accum=E4M3B15..., an explicit reduce-type code)
 U8, E4M3B15, E4M3B15_ACC_F16, E4M3B15_ACC_F32 = 11, 12, 13, 14
+# int64 / uint64 / int8: InProcessRanks.pull_reduce only, with all four ops (uint64 has no torch dtype
+# that indexes on the device: pass int64 tensors with accum=U64)
+I64, U64, I8 = 16, 17, 18
 SUM, MIN = 0, 1
 MAX, AVG = 2, 3  # InProcessRanks.pull_reduce only (ncclMax / ncclAvg: kernels/pull_reduce.hip)
 PULL_REDUCE, PULL_REDUCE_SCATTER, PULL_ALLREDUCE = 0, 1, 2
@@ -42,7 +45,7 @@ NCCL_DTYPES = {torch.float16: 6, torch.bfloat16: 9, torch.float32: 7, torch.int3
 NCCL_MOVE_DTYPES = {torch.int8: 0, torch.int64: 4, torch.float64: 8}
 NCCL_OPS = {"sum": 0, "min": 3, "max": 2, "avg": 4}
 DTYPE_CODES = {torch.float16: F16, torch.bfloat16: BF16, torch.float32: F32, torch.int32: I32, torch.uint8: U8,
-               torch.float8_e4m3fn: E4M3, torch.float8_e5m2: E5M2}
+               torch.float8_e4m3fn: E4M3, torch.float8_e5m2: E5M2, torch.int64: I64, torch.int8: I8}
 # accumulation dtype (ncclDataType_t) -> reduce-type code, for fp8 buffers
 ACCUM_CODES = {(torch.float8_e4m3fn, torch.float16): E4M3_ACC_F16, (torch.float8_e5m2, torch.float16): E5M2_ACC_F16,
                (torch.float8_e4m3fn, torch.float32): E4M3_ACC_F32, (torch.float8_e5m2, torch.float32): E5M2_ACC_F32}
@@ -516,11 +519,12 @@ class InProcessRanks:
 
     def pull_reduce(self, coll, inputs, outputs, op, root=0, nblocks=0, nthreads=0, budget_ticks=500_000_000,
                     stream=None, accum=None):
-        """ncclMax / ncclAvg (op = MAX / AVG) for in-process ranks, operands in rank order.  coll
+        """ncclMax / ncclAvg (op = MAX / AVG) for in-process ranks, operands in rank order; int64,
+        int8 and uint64 (accum=U64 over int64 tensors) tensors also take op = SUM / MIN.  coll
         PULL_REDUCE: outputs[root] <- the reduction of inputs (outputs[r] may be None elsewhere);
         PULL_REDUCE_SCATTER: inputs hold n blocks, outputs[r] <- block r reduced; PULL_ALLREDUCE: every
         outputs[r] <- the reduction.  Flat tensors; views at any element offset are carried.  accum: a
-        reduce-type code for the buffers (U32 over int32 tensors)."""
+        reduce-type code for the buffers (U32 over int32 tensors, U64 over int64 tensors)."""
         dt = reduce_code(inputs[0].dtype, accum)
         nbytes = inputs[0].numel() * inputs[0].element_size() // (self.n if coll == PULL_REDUCE_SCATTER else 1)
         arr = self.views(inputs, [inputs[r] if o is None else o for r, o in enumerate(outputs)])
@@ -608,7 +612,7 @@ class Communicator:
         """ncclAllReduce(send, recv, count, dtype, op, comm, stream); algo forces an algorithm, accum
         the accumulation dtype of Algorithm::execute (fp8 buffers: torch.float16 / torch.float32)."""
         recv = send if recv is None else recv
-        dt = NCCL_DTYPES[send.dtype]
+        dt = nccl_dtype(send.dtype)  # (int64 / int8: carried by the plain path alone; the forced ones refuse them)
         if accum is not None:
             code = lib().mscclppAmdCommAllReduceAccum(self.comm, ctypes.c_void_p(send.data_ptr()),
                                                       ctypes.c_void_p(recv.data_ptr()), send.numel(), dt,
@@ -629,7 +633,7 @@ class Communicator:
     def reduce_scatter(self, send, recv, op="sum", stream=None):
         """ncclReduceScatter(send, recv, recvcount, dtype, op, comm, stream)."""
         check(lib().ncclReduceScatter(ctypes.c_void_p(send.data_ptr()), ctypes.c_void_p(recv.data_ptr()), recv.numel(),
-                                      NCCL_DTYPES[send.dtype], NCCL_OPS[op], self.comm, stream_ptr(stream)),
+                                      nccl_dtype(send.dtype), NCCL_OPS[op], self.comm, stream_ptr(stream)),
               "ncclReduceScatter")
         return recv
 

@@ -458,7 +458,10 @@ ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, n
     if (!sendbuff || !recvbuff || count == 0 || tb == 0) return (int)ncclInvalidArgument;  // nccl.cc:617-622
     const int dt = dtypeFromNccl(datatype);
     const int o = opFromNccl(op), po = pullOpFromNccl(op);
-    if (comm->fallback && (dt < 0 || (o < 0 && po < 0) || forcedFallback("allreduce")))  // nccl.cc:628-632
+    // int64 / uint64 / int8: every operation the pull-reduce kernel computes for them, or nothing
+    const int pdt = pullOnlyDtypeFromNccl(datatype), pdo = pdt >= 0 ? pullOnlyOpFromNccl(op) : -1;
+    const bool carried = pdt >= 0 ? pdo >= 0 : dt >= 0 && (o >= 0 || po >= 0);
+    if (comm->fallback && (!carried || forcedFallback("allreduce")))  // nccl.cc:628-632
       return (int)vendorNccl()->AllReduce(sendbuff, recvbuff, count, datatype, op, (ncclComm_t)comm->fallback, stream);
     // every native path reads the send range (its own and, zero-copy, the peers') while receive ranges
     // are written: only the identical range (in place) may overlap
@@ -466,11 +469,13 @@ ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, n
       warn("ncclAllReduce: the send and receive ranges overlap without being identical");
       return (int)ncclInvalidArgument;
     }
+    if (pdt >= 0 && pdo >= 0)  // int64 / uint64 / int8, any of the four ops: the pull-reduce kernel
+      return comm->pullReduce(MSCCLPP_AMD_PULL_ALLREDUCE, sendbuff, recvbuff, bytes, pdt, pdo, 0, (hipStream_t)stream);
     if (dt >= 0 && po >= 0)  // ncclMax / ncclAvg: the pull-reduce kernel (no Algorithm: no selector is asked)
       return comm->pullReduce(MSCCLPP_AMD_PULL_ALLREDUCE, sendbuff, recvbuff, bytes, dt, po, 0, (hipStream_t)stream);
     if (dt < 0 || o < 0) {
-      warn("unsupported dtype/op for AllReduce (supported: fp16, bf16, fp32, int32, uint32, uint8, fp8 e4m3/e5m2 x sum, "
-           "min, max, avg)");
+      warn("unsupported dtype/op for AllReduce (supported: fp16, bf16, fp32, int32, uint32, uint8, int8, int64, uint64, "
+           "fp8 e4m3/e5m2 x sum, min, max, avg)");
       return (int)ncclInvalidArgument;
     }
     return selectAndExecute(comm, "allreduce", sendbuff, recvbuff, bytes, bytes, bytes, datatype, op, stream);
@@ -490,7 +495,9 @@ ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recv
     }
     if (!sendbuff || !recvbuff || recvcount == 0 || tb == 0) return (int)ncclInvalidArgument;
     const int dt = dtypeFromNccl(datatype), o = opFromNccl(op), po = pullOpFromNccl(op);
-    if (comm->fallback && (dt < 0 || (o < 0 && po < 0) || forcedFallback("reducescatter")))  // nccl.cc:682-686
+    const int pdt = pullOnlyDtypeFromNccl(datatype), pdo = pdt >= 0 ? pullOnlyOpFromNccl(op) : -1;  // as ncclAllReduce
+    const bool carried = pdt >= 0 ? pdo >= 0 : dt >= 0 && (o >= 0 || po >= 0);
+    if (comm->fallback && (!carried || forcedFallback("reducescatter")))  // nccl.cc:682-686
       return (int)vendorNccl()->ReduceScatter(sendbuff, recvbuff, recvcount, datatype, op, (ncclComm_t)comm->fallback,
                                               stream);
     // in place is recv == send + rank * bytes: a lane stores only units it has loaded, and the
@@ -500,6 +507,8 @@ ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recv
       warn("ncclReduceScatter: the receive range overlaps the send buffer elsewhere than at its own block");
       return (int)ncclInvalidArgument;
     }
+    if (pdt >= 0 && pdo >= 0)  // int64 / uint64 / int8, any of the four ops: the pull-reduce kernel
+      return comm->pullReduce(MSCCLPP_AMD_PULL_REDUCE_SCATTER, sendbuff, recvbuff, bytes, pdt, pdo, 0, (hipStream_t)stream);
     if (dt >= 0 && po >= 0)  // ncclMax / ncclAvg: the pull-reduce kernel (no Algorithm: no selector is asked)
       return comm->pullReduce(MSCCLPP_AMD_PULL_REDUCE_SCATTER, sendbuff, recvbuff, bytes, dt, po, 0, (hipStream_t)stream);
     if (dt < 0 || o < 0) return (int)ncclInvalidArgument;

@@ -211,6 +211,24 @@ inline int pullOpFromNccl(ncclRedOp_t op) {
   if (op == ncclAvg) return MSCCLPP_AMD_AVG;
   return -1;
 }
+// ncclInt64 / ncclUint64 / ncclInt8: carried by the pull-reduce kernel alone, so they have a mapper
+// of their own and dtypeFromNccl keeps answering -1 for them -- its other callers (the selector, the
+// forced-algorithm entry points, the accumulation-type API) must keep refusing them.
+inline int pullOnlyDtypeFromNccl(ncclDataType_t t) {
+  switch (t) {
+    case ncclInt64: return MSCCLPP_AMD_I64;
+    case ncclUint64: return MSCCLPP_AMD_U64;
+    case ncclInt8: return MSCCLPP_AMD_I8;
+    default: return -1;
+  }
+}
+// ... for which that kernel also computes SUM and MIN (the other types take those to their own
+// kernels); -1 for every other operation (ncclProd, PreMulSum handles).
+inline int pullOnlyOpFromNccl(ncclRedOp_t op) {
+  if (op == ncclSum) return MSCCLPP_AMD_SUM;
+  if (op == ncclMin) return MSCCLPP_AMD_MIN;
+  return pullOpFromNccl(op);
+}
 inline bool bufferRangesOverlap(const void* a, size_t na, const void* b, size_t nb) {
   const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
   return x < y + nb && y < x + na;
@@ -744,9 +762,9 @@ struct ncclComm {
     return rc;
   }
 
-  // ncclMax / ncclAvg of Reduce, ReduceScatter and AllReduce (kernels/pull_reduce.hip; DESIGN.md
-  // §17d), the pattern of reduce(): the send buffer is what the peers read, so it is registered on
-  // every rank; an AllReduce's peers also read this rank's reduced slice out of its receive buffer,
+  // ncclMax / ncclAvg of Reduce, ReduceScatter and AllReduce, and every operation of int64 / uint64 /
+  // int8 (kernels/pull_reduce.hip), the pattern of reduce(): the send buffer is
+  // what the peers read, so it is registered on every rank; an AllReduce's peers also read this rank's reduced slice out of its receive buffer,
   // which is registered too (the same registration when in place).  bytes: the message of Reduce /
   // AllReduce, the per-rank block of ReduceScatter.  Every rank derives the same grid from (coll, bytes).
   int pullReduce(int coll, const void* send, void* recv, size_t bytes, int dtype, int op, int root, hipStream_t stream) {

@@ -4,7 +4,8 @@
 //  * native here: ncclBroadcast / ncclBcast (zero-copy pull from the root), ncclAllToAll /
 //    ncclAllToAllv (zero-copy pull from every peer, kernels/alltoall.hip; the reference leaves both
 //    to the vendor library, nccl.cc:794-821), ncclReduce (zero-copy pull-reduce at the root,
-//    kernels/reduce.hip, for the data types and operations AllReduce carries; the reference returns
+//    kernels/reduce.hip, for the data types and operations AllReduce carries -- ncclMax / ncclAvg and
+//    every operation of int64 / uint64 / int8 by kernels/pull_reduce.hip; the reference returns
 //    ncclInternalError without a vendor library, nccl.cc:521-542), ncclSend / ncclRecv between two
 //    different ranks, alone or inside ncclGroupStart / ncclGroupEnd (zero-copy pull by the receiver,
 //    kernels/sendrecv.hip; the reference: nccl.cc:774-792), ncclCommSplit (nccl.cc:405-435),
@@ -378,8 +379,13 @@ ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, nccl
       return (int)ncclInvalidArgument;
     }
     const int dt = dtypeFromNccl(datatype), o = opFromNccl(op), po = pullOpFromNccl(op);
-    if (vendorComm(comm) && vendorNccl()->Reduce && (dt < 0 || (o < 0 && po < 0) || forcedFallback("reduce")))
+    const int pdt = pullOnlyDtypeFromNccl(datatype), pdo = pdt >= 0 ? pullOnlyOpFromNccl(op) : -1;  // as ncclAllReduce
+    const bool carried = pdt >= 0 ? pdo >= 0 : dt >= 0 && (o >= 0 || po >= 0);
+    if (vendorComm(comm) && vendorNccl()->Reduce && (!carried || forcedFallback("reduce")))
       return (int)vendorNccl()->Reduce(sendbuff, recvbuff, count, datatype, op, root, vendorComm(comm), stream);
+    if (pdt >= 0 && pdo >= 0)  // int64 / uint64 / int8, any of the four ops: the pull-reduce kernel
+      return comm->pullReduce(MSCCLPP_AMD_PULL_REDUCE, sendbuff, isRoot ? recvbuff : nullptr, bytes, pdt, pdo, root,
+                              (hipStream_t)stream);
     if (dt >= 0 && po >= 0)  // ncclMax / ncclAvg: the pull-reduce kernel, rank order (kernels/pull_reduce.hip)
       return comm->pullReduce(MSCCLPP_AMD_PULL_REDUCE, sendbuff, isRoot ? recvbuff : nullptr, bytes, dt, po, root,
                               (hipStream_t)stream);
@@ -660,16 +666,20 @@ int mscclppAmdSendRecvLaunch(const mscclppAmdRankView* views, int nviews, int nr
 
 int mscclppAmdSendRecvDefaultBlocks(uint64_t bytes) { return mscclpp_amd::sendrecvDefaultBlocks(bytes); }
 
-// ncclMax / ncclAvg of Reduce / ReduceScatter / AllReduce for in-process ranks (and the one-view
-// form the NCCL entry points launch): everything is checked before a device is touched; a refusal
-// launches nothing.
+// ncclMax / ncclAvg of Reduce / ReduceScatter / AllReduce, and the four operations of int64 / uint64 /
+// int8, for in-process ranks (and the one-view form the NCCL entry points launch): everything is
+// checked before a device is touched; a refusal launches nothing.
 int mscclppAmdPullReduceLaunch(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes, int dtype,
                                int op, int root, int nblocks, int nthreads, uint64_t budgetTicks, void* stream) {
   return guarded([&] {
     if (coll < MSCCLPP_AMD_PULL_REDUCE || coll > MSCCLPP_AMD_PULL_ALLREDUCE) return (int)ncclInvalidArgument;
     const bool reduce = coll == MSCCLPP_AMD_PULL_REDUCE, all = coll == MSCCLPP_AMD_PULL_ALLREDUCE;
     if (reduce && (root < 0 || root >= nranks)) return (int)ncclInvalidArgument;
-    if (op != MSCCLPP_AMD_MAX && op != MSCCLPP_AMD_AVG) return (int)ncclInvalidArgument;  // SUM / MIN: their own kernels
+    // SUM / MIN of the eight types that have their own kernels for them are refused; of int64 / uint64 /
+    // int8, which have no other kernel, they are taken
+    const bool pullOnly = dtype == MSCCLPP_AMD_I64 || dtype == MSCCLPP_AMD_U64 || dtype == MSCCLPP_AMD_I8;
+    if (op != MSCCLPP_AMD_MAX && op != MSCCLPP_AMD_AVG && !(pullOnly && (op == MSCCLPP_AMD_SUM || op == MSCCLPP_AMD_MIN)))
+      return (int)ncclInvalidArgument;
     if (bytes == 0) return (int)ncclInvalidArgument;  // (the dtype codes and a split element: launchPullReduce)
     // what moves data: every view, but for Reduce the root's alone (the others read and write no user memory)
     const unsigned moves = kViewOutput | kViewPeerInput | (all ? kViewPeerOutput : 0u);

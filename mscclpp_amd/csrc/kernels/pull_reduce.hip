@@ -1,6 +1,8 @@
-// ncclMax / ncclAvg for Reduce, ReduceScatter and AllReduce: one zero-copy pull-reduce kernel.
+// ncclMax / ncclAvg for Reduce, ReduceScatter and AllReduce, and SUM / MIN / MAX / AVG of int64, uint64
+// and int8: one zero-copy pull-reduce kernel.
 //
-// The reference carries SUM and MIN (and leaves the other operations to the vendor library), so
+// The reference carries SUM and MIN of fp16, bf16, fp32, int32, uint32, uint8 and fp8 (and leaves the
+// other operations and types to the vendor library), so
 // this is no restatement; the arithmetic is defined in mscclpp_amd/pull_reduce_device.hpp.  As in
 // reduce.hip every load of a peer's memory is a system-scope 16-byte buffer load of its user
 // buffer in place, the reduction happens in registers, and every store is a plain store into the
@@ -28,6 +30,9 @@
 //    waited for) before the token add; the peer reads with system-scope loads after its acquire.
 //    Write-through (sc0 sc1) stores would drop the lines from the L2 that the same rank's next
 //    kernel reads the result from, for no gain: the release is paid by the handshake anyway.
+//  * 64-bit elements span two words of a unit: their accumulators take and return a word pair
+//    (pull_acc_words).  A range that ends on an odd 64-bit element has an 8-byte tail, moved byte by
+//    byte like any other; the zero-filled rest of that unit is reduced and not stored.
 //  * Exit handshake: every reader is done with this rank's send and receive buffers.
 //  * Tails and alignment as reduce.hip: the last unit of a range that is no multiple of 16 bytes
 //    moves byte by byte; no byte outside [recv + dstOff, + len) is written and none outside a send
@@ -40,8 +45,9 @@
 
 namespace mscclpp_amd {
 
-// Units per lane in flight, from the resource report of the 32 instantiations (hipcc
-// -Rpass-analysis=kernel-resource-usage; DESIGN.md §17d has the table; none uses scratch).  As for
+// Units per lane in flight, from the resource report of the 56 instantiations (hipcc
+// -Rpass-analysis=kernel-resource-usage; DESIGN.md §17d and §17e have the tables; none uses scratch,
+// and the 64-bit AVG stays at 96 VGPRs with U = 2, so no instantiation needs a U of its own).  As for
 // reduceKernel, U = 2 keeps 256 bytes of loads per lane in flight at 8 ranks and stays at or below
 // 128 VGPRs, i.e. two 512-lane workgroups per CU, which the in-process launch of 8 ranks x 64
 // workgroups needs to be resident at once.
@@ -105,14 +111,28 @@ __global__ void __launch_bounds__(512) pullReduceKernel(PullReduceArgs<NV> a) {
         if (vb[i] == 0) continue;
         const uint32_t u = u0 + i * T;
         u32x4 r;
+        if constexpr (pull_acc_words(DT) == 2) {  // a 64-bit element: words j (low) and j + 1
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          PullAcc<DT, OP> acc;
-          acc.first(w[i][0][j]);
+          for (int j = 0; j < 4; j += 2) {
+            PullAcc<DT, OP> acc;
+            acc.first(w[i][0][j] | (uint64_t)w[i][0][j + 1] << 32);
 #pragma unroll
-          for (int k = 1; k < kMaxRanks; ++k)
-            if (k < n) acc.next(w[i][k][j]);
-          r[j] = acc.word(n, a.invN);
+            for (int k = 1; k < kMaxRanks; ++k)
+              if (k < n) acc.next(w[i][k][j] | (uint64_t)w[i][k][j + 1] << 32);
+            const uint64_t e = acc.word(n, a.invN);
+            r[j] = (uint32_t)e;
+            r[j + 1] = (uint32_t)(e >> 32);
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            PullAcc<DT, OP> acc;
+            acc.first(w[i][0][j]);
+#pragma unroll
+            for (int k = 1; k < kMaxRanks; ++k)
+              if (k < n) acc.next(w[i][k][j]);
+            r[j] = acc.word(n, a.invN);
+          }
         }
         store_payload<kPlain>(rout, dst, (uint64_t)u * 16, r, vb[i]);
       }
@@ -214,6 +234,11 @@ static int launchPullReduceT(const mscclppAmdRankView* views, int nviews, int nr
 #define MSCCLPP_AMD_PULL_CASE2(DT, ...)                                            \
   case DT * 4 + kPullMax: return launchPullReduceT<DT, kPullMax>(__VA_ARGS__);     \
   case DT * 4 + kPullAvg: return launchPullReduceT<DT, kPullAvg>(__VA_ARGS__);
+// int64 / uint64 / int8: SUM and MIN as well (the other types take those to their own kernels)
+#define MSCCLPP_AMD_PULL_CASE4(DT, ...)                                            \
+  case DT * 4 + kSum: return launchPullReduceT<DT, kSum>(__VA_ARGS__);             \
+  case DT * 4 + kMin: return launchPullReduceT<DT, kMin>(__VA_ARGS__);             \
+  MSCCLPP_AMD_PULL_CASE2(DT, __VA_ARGS__)
 
 int launchPullReduce(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes, int dtype, int op,
                      int root, int nblocks, int nthreads, uint64_t budget, hipStream_t s) {
@@ -222,7 +247,7 @@ int launchPullReduce(const mscclppAmdRankView* views, int nviews, int nranks, in
   if (!launchShapeOk(nblocks, kMaxChannels, nthreads)) return 4;
   if (nranks < 2 || nranks > kMaxRanks || bytes == 0) return 4;
   if (coll == MSCCLPP_AMD_PULL_REDUCE && (root < 0 || root >= nranks)) return 4;
-  if ((op != kPullMax && op != kPullAvg) || !pull_reduce_carries(dtype) || bytes % (size_t)elem_bytes(dtype)) return 4;
+  if (!pull_reduce_takes(dtype, op) || bytes % (size_t)elem_bytes(dtype)) return 4;
   uint64_t srcOff[kMaxRanks], dstOff[kMaxRanks], len[kMaxRanks];
   const uint64_t most = pullReduceGeometry(coll, nranks, bytes, root, srcOff, dstOff, len);
   const uint64_t blk = blockBytes(most, (uint32_t)nblocks);
@@ -236,6 +261,9 @@ int launchPullReduce(const mscclppAmdRankView* views, int nviews, int nranks, in
     MSCCLPP_AMD_PULL_CASE2(kE4M3, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)
     MSCCLPP_AMD_PULL_CASE2(kE5M2, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)
     MSCCLPP_AMD_PULL_CASE2(kU8, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)
+    MSCCLPP_AMD_PULL_CASE4(kI64, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)
+    MSCCLPP_AMD_PULL_CASE4(kU64, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)
+    MSCCLPP_AMD_PULL_CASE4(kI8, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)
     default: return 4;
   }
 }

@@ -16,6 +16,11 @@ reads (rsag_zc: half reads, half remote stores); whether reads beat remote store
 links this tool cannot say.
 
     python tools/pull_reduce_perf.py   (writes profiles/pull_reduce_perf_inprocess_n8.json, or $OUT)
+
+TYPES=int64 runs another, shorter programme instead: int64 SUM and AVG beside fp32 MAX
+at the same byte counts, default grids, the three collectives, alternating in the same run; SIZES
+defaults to 8 bytes, 1 MiB and 48 MiB (a ReduceScatter needs n elements), and the result goes to
+profiles/int_reduce_perf_inprocess_n8.json.
 """
 import json
 import os
@@ -65,6 +70,71 @@ def stat(v):
 
 def cur():
     return torch.cuda.current_stream()
+
+
+def int64_programme():
+    sizes = [int(s) for s in os.environ.get("SIZES", f"8,{1 << 20},{48 << 20}").split(",")]
+    rows = []
+    for S in sizes:
+        ranks = m.InProcessRanks(N, 1 << 16)
+        bufs = {}
+        for name, tdt, es in (("i64", torch.int64, 8), ("f32", torch.float32, 4)):
+            count = S // es
+            if tdt == torch.int64:  # all 64 bits: sums wrap, averages need the 67-bit sum
+                sends = [(torch.randint(-2 ** 31, 2 ** 31, (count,), dtype=tdt, device=dev) << 32) |
+                         torch.randint(0, 2 ** 32, (count,), dtype=tdt, device=dev) for _ in range(N)]
+            else:
+                sends = [torch.rand(count, dtype=tdt, device=dev) for _ in range(N)]
+            full = [torch.zeros(count, dtype=tdt, device=dev) for _ in range(N)]
+            blk = count // N
+            part = [torch.zeros(max(blk, 1), dtype=tdt, device=dev) for _ in range(N)]
+            bufs[name] = (sends, {m.PULL_ALLREDUCE: (sends, full), m.PULL_REDUCE_SCATTER: ([t[:blk * N] for t in sends], part),
+                                  m.PULL_REDUCE: (sends, [full[r] if r == ROOT_RANK else None for r in range(N)])})
+        colls = [(name, c) for name, c in COLLS if c != m.PULL_REDUCE_SCATTER or S // 8 >= N]
+
+        def call(name, coll, op):
+            ins, outs = bufs[name][1][coll]
+            ranks.pull_reduce(coll, ins, outs, op, root=ROOT_RANK, budget_ticks=BUDGET, stream=cur())
+
+        # correctness of what is timed: the wrapping sum everywhere, the exact average on a sample
+        x = bufs["i64"][0]
+        full = bufs["i64"][1][m.PULL_ALLREDUCE][1]
+        call("i64", m.PULL_ALLREDUCE, m.SUM)
+        torch.cuda.synchronize()
+        ok = all(torch.equal(t, torch.stack(x).sum(dim=0)) for t in full)
+        call("i64", m.PULL_ALLREDUCE, m.AVG)
+        torch.cuda.synchronize()
+        for i in range(0, S // 8, max(1, S // 8 // 61)):
+            s = sum(int(t[i].item()) for t in x)
+            ok = ok and int(full[0][i].item()) == abs(s) // N * (1 if s >= 0 else -1)
+        ok = ok and ranks.errors() == [0] * N
+        calls, replays = (10, 5) if S >= (8 << 20) else (50, 10)
+        lines = [(f"{cname}_{label}", (lambda b=b, c=c, op=op: call(b, c, op)))
+                 for cname, c in colls for label, b, op in (("i64_sum", "i64", m.SUM), ("i64_avg", "i64", m.AVG),
+                                                            ("f32_max", "f32", m.MAX))]
+        t = {name: [] for name, _ in lines}
+        for _ in range(ROUNDS):
+            for name, fn in lines:
+                t[name].append(graph_us(fn, calls, replays))
+        row = {"send_bytes_per_rank": S, "root": ROOT_RANK, "correct": bool(ok), "graph_calls": calls, "replays": replays,
+               "rounds": ROUNDS,
+               "default_nblocks": {name: m.lib().mscclppAmdPullReduceDefaultBlocks(c, S // N if c == m.PULL_REDUCE_SCATTER else S)
+                                   for name, c in colls},
+               "lines": {name: stat(v) for name, v in t.items()}, "errors": ranks.errors()}
+        rows.append(row)
+        print(row, flush=True)
+        del bufs, ranks
+    res = {"tool": "tools/pull_reduce_perf.py TYPES=int64", "fabric_free": True, "gpus": 1, "nranks": N,
+           "note": "in-process ranks on one GPU: no xGMI byte is priced; graph-captured, median of rounds", "rows": rows}
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = os.environ.get("OUT", os.path.join(root, "profiles", f"int_reduce_perf_inprocess_n{N}.json"))
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    json.dump(res, open(out, "w"), indent=1)
+
+
+if os.environ.get("TYPES") == "int64":
+    int64_programme()
+    sys.exit(0)
 
 
 rows = []
