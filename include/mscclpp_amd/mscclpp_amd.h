@@ -57,6 +57,10 @@ enum { MSCCLPP_AMD_SUM = 0, MSCCLPP_AMD_MIN = 1 };
 /* ncclMax / ncclAvg: accepted ONLY by mscclppAmdPullReduceLaunch (and through it by ncclAllReduce /
  * ncclReduceScatter / ncclReduce); every other entry point keeps the op range SUM .. MIN. */
 enum { MSCCLPP_AMD_MAX = 2, MSCCLPP_AMD_AVG = 3 };
+/* PreMulSum (ncclRedOpCreatePreMulSum): accepted ONLY by mscclppAmdPullReduceLaunchScaled (and through
+ * it by ncclAllReduce / ncclReduceScatter / ncclReduce with a live handle), with F16, BF16 and F32.
+ * Code 4 names nothing and stays refused everywhere. */
+enum { MSCCLPP_AMD_PREMUL_SUM = 5 };
 /* int64 / uint64 / int8 (ncclInt64 / ncclUint64 / ncclInt8): likewise accepted ONLY by
  * mscclppAmdPullReduceLaunch (and through it by ncclAllReduce / ncclReduceScatter / ncclReduce), there
  * with all of SUM, MIN, MAX and AVG.  They lie beyond MSCCLPP_AMD_NUM_DTYPES, which keeps bounding the
@@ -238,6 +242,18 @@ int mscclppAmdReduceLaunch(const mscclppAmdRankView* views, int nviews, int nran
  * cannot be resident at once. */
 int mscclppAmdPullReduceLaunch(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes, int dtype,
                                int op, int root, int nblocks, int nthreads, uint64_t budgetTicks, void* stream);
+/* PreMulSum by the same kernel: op MSCCLPP_AMD_PREMUL_SUM with dtype F16, BF16 or F32 only.  The view
+ * of rank k multiplies rank k's operand by rank k's scalar (one fp32 multiply, rounded before the fp32
+ * sum in rank order; the sum is rounded once to the element type: pull_reduce_device.hpp), so the
+ * scalars may differ between ranks; the kernel exchanges them itself.  scales: host array, one fp32
+ * per view (the scalar of views[i].rank; a caller holding it in the element type decodes it, which
+ * is exact).  scalePtrs: NULL, or a host array of one pointer per view; a non-null entry overrides
+ * that view's immediate and points to ONE element of the element type in device memory, read when
+ * the kernel runs (so a graph replay reads the value of its own time).  Everything else, and every
+ * refusal, is as for mscclppAmdPullReduceLaunch; NULL scales, and any other op or dtype, answer 4. */
+int mscclppAmdPullReduceLaunchScaled(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes,
+                                     int dtype, int op, int root, int nblocks, int nthreads, uint64_t budgetTicks,
+                                     void* stream, const float* scales, const void* const* scalePtrs);
 int mscclppAmdPullReduceDefaultBlocks(int coll, uint64_t bytes);
 /* Send / Recv by a zero-copy pull (kernels/sendrecv.hip): one launch runs a table of point-to-point
  * operations, in table order.  An operation moves `bytes` from `send` on rank `src` to `recv` on

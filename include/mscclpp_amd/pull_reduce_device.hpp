@@ -27,6 +27,14 @@
 //           hi < n, and with c1 = floor(2^64 / n), c2 = 2^64 mod n (constants per n)
 //           M / n = hi * c1 + lo / n + (hi * c2 + lo % n) / n: one 64-bit divide by a constant per
 //           element; the sign is put back afterwards.
+//  * PreMulSum (ncclRedOpCreatePreMulSum; kPullPreMulSum), fp16 / bf16 / fp32: every rank k has a
+//    scalar s_k of its own, given in the element type; rank k's operand is multiplied by rank k's
+//    scalar (NCCL's rule: the input is pre-multiplied locally), so the scalars may differ between
+//    ranks.  x_k and s_k decode exactly to fp32; p_k = x_k * s_k is ONE fp32 RNE multiply and a value
+//    of its own (no multiply fuses with the following add: fp32_product); acc = p_0, then
+//    acc = acc + p_k for k = 1 .. n - 1, one fp32 RNE add each; acc is rounded ONCE to the element
+//    type exactly as AVG's result is (fp32 as is, (_Float16)acc, (__bf16)acc).  NCCL multiplies fp16
+//    and bf16 operands in half precision; the fp32 product here is the more precise one.
 #pragma once
 
 #include "reduce_device.hpp"
@@ -35,7 +43,10 @@ namespace mscclpp_amd {
 
 // Operation codes of the pull-reduce path only (MSCCLPP_AMD_MAX / MSCCLPP_AMD_AVG); the <DT, OP>
 // kernels of ROp keep their range.
-enum PullOp : int { kPullMax = 2, kPullAvg = 3 };
+enum PullOp : int { kPullMax = 2, kPullAvg = 3, kPullPreMulSum = 5 };  // (4 stays refused)
+
+// PreMulSum: the three float types a framework passes (bar double).
+__host__ __device__ constexpr bool pull_premul_type(int dt) { return dt == kF16 || dt == kBF16 || dt == kF32; }
 
 // int64 / uint64 / int8: carried by this path alone, with kSum and kMin as well.
 __host__ __device__ constexpr bool pull_only_type(int dt) { return dt == kI64 || dt == kU64 || dt == kI8; }
@@ -46,10 +57,12 @@ __host__ __device__ constexpr bool pull_reduce_carries(int dt) {
   return dt == kF16 || dt == kBF16 || dt == kF32 || dt == kI32 || dt == kU32 || dt == kE4M3 || dt == kE5M2 ||
          dt == kU8 || pull_only_type(dt);
 }
-// MAX / AVG for every carried type; SUM / MIN exactly for the three types that have no other kernel.
+// MAX / AVG for every carried type; SUM / MIN exactly for the three types that have no other kernel;
+// PreMulSum for the three float types.
 __host__ __device__ constexpr bool pull_reduce_takes(int dt, int op) {
   return pull_reduce_carries(dt) &&
-         (op == kPullMax || op == kPullAvg || ((op == kSum || op == kMin) && pull_only_type(dt)));
+         (op == kPullMax || op == kPullAvg || ((op == kSum || op == kMin) && pull_only_type(dt)) ||
+          (op == kPullPreMulSum && pull_premul_type(dt)));
 }
 // 32-bit words an accumulator consumes at a time: 2 for the 64-bit types (first / next take and
 // word() returns a uint64_t), 1 for every other type.
@@ -79,6 +92,21 @@ __device__ __forceinline__ T div_ranks(T s, int n) {
 // (An empty asm statement: no instruction, only the register constraint.)
 __device__ __forceinline__ float fp32_product(float s, float inv) {
   float r = s * inv;
+  asm("" : "+v"(r));
+  return r;
+}
+
+// The fp32 sum of PreMulSum as a value of its own before it is rounded to the element type, for the
+// same reason: no conversion is selected together with the add that produced it.
+__device__ __forceinline__ float fp32_value(float r) {
+  asm("" : "+v"(r));
+  return r;
+}
+
+// Two fp32 products at once (v_pk_mul_f32), each a value of its own as in fp32_product: the halves of
+// a 16-bit pair times one scalar (PreMulSum).
+__device__ __forceinline__ float2_t fp32_product2(float2_t x, float s) {
+  float2_t r = x * s;
   asm("" : "+v"(r));
   return r;
 }
@@ -170,6 +198,57 @@ struct PullAcc<kBF16, kPullAvg> {
     return (uint32_t)__builtin_bit_cast(uint16_t, l) | ((uint32_t)__builtin_bit_cast(uint16_t, h) << 16);
   }
 };
+
+// ---- PreMulSum: first / next also take the operand's rank's scalar ---------------------------------
+// Every product goes through fp32_product, so it is rounded to fp32 before the add that follows.
+template <>
+struct PullAcc<kF32, kPullPreMulSum> {
+  float s;
+  __device__ __forceinline__ void first(uint32_t w, float sc) { s = fp32_product(__builtin_bit_cast(float, w), sc); }
+  __device__ __forceinline__ void next(uint32_t w, float sc) { s = s + fp32_product(__builtin_bit_cast(float, w), sc); }
+  __device__ __forceinline__ uint32_t word(int, float) const { return __builtin_bit_cast(uint32_t, s); }
+};
+
+template <>
+struct PullAcc<kF16, kPullPreMulSum> {
+  float2_t a;  // {low half, high half}
+  __device__ __forceinline__ void first(uint32_t w, float sc) {
+    a = fp32_product2(float2_t{f16_to_f32(w & 0xffffu), f16_to_f32(w >> 16)}, sc);
+  }
+  __device__ __forceinline__ void next(uint32_t w, float sc) {
+    a = a + fp32_product2(float2_t{f16_to_f32(w & 0xffffu), f16_to_f32(w >> 16)}, sc);
+  }
+  __device__ __forceinline__ uint32_t word(int, float) const {
+    const _Float16 l = (_Float16)fp32_value(a.x), h = (_Float16)fp32_value(a.y);
+    return (uint32_t)__builtin_bit_cast(uint16_t, l) | ((uint32_t)__builtin_bit_cast(uint16_t, h) << 16);
+  }
+};
+
+template <>
+struct PullAcc<kBF16, kPullPreMulSum> {
+  float2_t a;  // {low half, high half}
+  __device__ __forceinline__ void first(uint32_t w, float sc) { a = fp32_product2(float2_t{bf16_lo(w), bf16_hi(w)}, sc); }
+  __device__ __forceinline__ void next(uint32_t w, float sc) {
+    a = a + fp32_product2(float2_t{bf16_lo(w), bf16_hi(w)}, sc);
+  }
+  __device__ __forceinline__ uint32_t word(int, float) const {
+    const __bf16 l = (__bf16)fp32_value(a.x), h = (__bf16)fp32_value(a.y);
+    return (uint32_t)__builtin_bit_cast(uint16_t, l) | ((uint32_t)__builtin_bit_cast(uint16_t, h) << 16);
+  }
+};
+
+// A rank's scalar, given as one element of the element type, decoded exactly to fp32 (the device-
+// resident form of ncclRedOpCreatePreMulSum: read when the kernel runs).
+template <int DT>
+__device__ __forceinline__ float premul_scalar_at(const void* p) {
+  if constexpr (DT == kF32) {
+    return *(const float*)p;
+  } else if constexpr (DT == kF16) {
+    return f16_to_f32(*(const uint16_t*)p);
+  } else {
+    return bf16_lo(*(const uint16_t*)p);
+  }
+}
 
 template <int DT>
 struct PullAccFp8Avg {

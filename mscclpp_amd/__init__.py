@@ -29,6 +29,10 @@ U8, E4M3B15, E4M3B15_ACC_F16, E4M3B15_ACC_F32 = 11, 12, 13, 14
 I64, U64, I8 = 16, 17, 18
 SUM, MIN = 0, 1
 MAX, AVG = 2, 3  # InProcessRanks.pull_reduce only (ncclMax / ncclAvg: kernels/pull_reduce.hip)
+# ncclRedOpCreatePreMulSum: InProcessRanks.pull_reduce(..., scales=...) with float16 / bfloat16 / float32
+# (rank k's operand times rank k's scalar, summed in rank order; 4 names nothing and is refused)
+PREMUL_SUM = 5
+SCALAR_DEVICE, SCALAR_HOST_IMMEDIATE = 0, 1  # ncclScalarResidence_t
 PULL_REDUCE, PULL_REDUCE_SCATTER, PULL_ALLREDUCE = 0, 1, 2
 ALGO_AUTO, ALGO_PACKET, ALGO_ALLPAIR, ALGO_FULLMESH, ALGO_RSAG, ALGO_RSAG_ZC, ALGO_RSAG_PIPELINE = 0, 1, 2, 3, 4, 5, 6
 ALGO_TEST_K2, ALGO_TEST_K5, ALGO_TEST_K6, ALGO_TEST_K7 = 102, 105, 106, 107  # mscclpp-test allreduce2/5/6/7 (int32)
@@ -49,6 +53,11 @@ DTYPE_CODES = {torch.float16: F16, torch.bfloat16: BF16, torch.float32: F32, tor
 # accumulation dtype (ncclDataType_t) -> reduce-type code, for fp8 buffers
 ACCUM_CODES = {(torch.float8_e4m3fn, torch.float16): E4M3_ACC_F16, (torch.float8_e5m2, torch.float16): E5M2_ACC_F16,
                (torch.float8_e4m3fn, torch.float32): E4M3_ACC_F32, (torch.float8_e5m2, torch.float32): E5M2_ACC_F32}
+
+
+def nccl_op(op):
+    """ncclRedOp_t of an operation's name, or of a handle (an int: Communicator.create_premul_sum)."""
+    return NCCL_OPS[op] if isinstance(op, str) else int(op)
 
 
 def nccl_dtype(dtype):
@@ -161,7 +170,11 @@ def lib():
         "mscclppAmdReduceLaunch": [ctypes.POINTER(RankView), i32, i32, sz, i32, i32, i32, i32, i32, u64, vp],
         "ncclReduce": [vp, vp, sz, i32, i32, i32, vp, vp],
         "mscclppAmdPullReduceLaunch": [ctypes.POINTER(RankView), i32, i32, i32, sz, i32, i32, i32, i32, i32, u64, vp],
+        "mscclppAmdPullReduceLaunchScaled": [ctypes.POINTER(RankView), i32, i32, i32, sz, i32, i32, i32, i32, i32, u64, vp,
+                                             ctypes.POINTER(ctypes.c_float), ctypes.POINTER(vp)],
         "mscclppAmdPullReduceDefaultBlocks": [i32, u64],
+        "ncclRedOpCreatePreMulSum": [ctypes.POINTER(i32), vp, i32, i32, vp],
+        "ncclRedOpDestroy": [i32, vp],
         "mscclppAmdSendRecvLaunch": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(SendRecvOp), i32, i32, i32, u64, vp],
         "mscclppAmdSendRecvDefaultBlocks": [u64],
         "ncclSend": [vp, sz, i32, i32, vp, vp],
@@ -518,13 +531,17 @@ class InProcessRanks:
         check(code, "in-process reduce")
 
     def pull_reduce(self, coll, inputs, outputs, op, root=0, nblocks=0, nthreads=0, budget_ticks=500_000_000,
-                    stream=None, accum=None):
+                    stream=None, accum=None, scales=None, scale_tensors=None):
         """ncclMax / ncclAvg (op = MAX / AVG) for in-process ranks, operands in rank order; int64,
         int8 and uint64 (accum=U64 over int64 tensors) tensors also take op = SUM / MIN.  coll
         PULL_REDUCE: outputs[root] <- the reduction of inputs (outputs[r] may be None elsewhere);
         PULL_REDUCE_SCATTER: inputs hold n blocks, outputs[r] <- block r reduced; PULL_ALLREDUCE: every
         outputs[r] <- the reduction.  Flat tensors; views at any element offset are carried.  accum: a
-        reduce-type code for the buffers (U32 over int32 tensors, U64 over int64 tensors)."""
+        reduce-type code for the buffers (U32 over int32 tensors, U64 over int64 tensors).
+        op = PREMUL_SUM (float16 / bfloat16 / float32): scales[r] is rank r's scalar, a Python float that
+        the element type holds exactly; scale_tensors[r], where given and not None, overrides it: a device
+        tensor of the element type whose first element the kernel reads when it runs.  Passing either
+        takes the scaled entry point, which refuses every other op."""
         dt = reduce_code(inputs[0].dtype, accum)
         nbytes = inputs[0].numel() * inputs[0].element_size() // (self.n if coll == PULL_REDUCE_SCATTER else 1)
         arr = self.views(inputs, [inputs[r] if o is None else o for r, o in enumerate(outputs)])
@@ -533,8 +550,16 @@ class InProcessRanks:
                 arr[r].output = None
                 for q in range(self.n):
                     arr[q].peerOutput[r] = None
-        code = lib().mscclppAmdPullReduceLaunch(arr, self.n, self.n, coll, nbytes, dt, op, root, nblocks, nthreads,
-                                                budget_ticks, stream_ptr(stream))
+        if scales is None and scale_tensors is None:
+            code = lib().mscclppAmdPullReduceLaunch(arr, self.n, self.n, coll, nbytes, dt, op, root, nblocks, nthreads,
+                                                    budget_ticks, stream_ptr(stream))
+        else:
+            imm = (ctypes.c_float * self.n)(*(scales if scales is not None else [0.0] * self.n))
+            ptrs = None
+            if scale_tensors is not None:
+                ptrs = (ctypes.c_void_p * self.n)(*[None if t is None else t.data_ptr() for t in scale_tensors])
+            code = lib().mscclppAmdPullReduceLaunchScaled(arr, self.n, self.n, coll, nbytes, dt, op, root, nblocks,
+                                                          nthreads, budget_ticks, stream_ptr(stream), imm, ptrs)
         check(code, "in-process pull_reduce")
 
     def send_recv(self, ops, nblocks=0, nthreads=0, budget_ticks=500_000_000, stream=None):
@@ -616,15 +641,15 @@ class Communicator:
         if accum is not None:
             code = lib().mscclppAmdCommAllReduceAccum(self.comm, ctypes.c_void_p(send.data_ptr()),
                                                       ctypes.c_void_p(recv.data_ptr()), send.numel(), dt,
-                                                      NCCL_OPS[op], NCCL_DTYPES[accum],
+                                                      nccl_op(op), NCCL_DTYPES[accum],
                                                       ALGO_NAMES.get(algo or "auto", algo) if isinstance(algo, str) or algo is None else algo,
                                                       nblocks, nthreads, stream_ptr(stream))
         elif algo is None:
             code = lib().ncclAllReduce(ctypes.c_void_p(send.data_ptr()), ctypes.c_void_p(recv.data_ptr()),
-                                       send.numel(), dt, NCCL_OPS[op], self.comm, stream_ptr(stream))
+                                       send.numel(), dt, nccl_op(op), self.comm, stream_ptr(stream))
         else:
             code = lib().mscclppAmdCommAllReduce(self.comm, ctypes.c_void_p(send.data_ptr()),
-                                                 ctypes.c_void_p(recv.data_ptr()), send.numel(), dt, NCCL_OPS[op],
+                                                 ctypes.c_void_p(recv.data_ptr()), send.numel(), dt, nccl_op(op),
                                                  ALGO_NAMES.get(algo, algo) if isinstance(algo, str) else algo,
                                                  nblocks, nthreads, stream_ptr(stream))
         check(code, "ncclAllReduce")
@@ -633,7 +658,7 @@ class Communicator:
     def reduce_scatter(self, send, recv, op="sum", stream=None):
         """ncclReduceScatter(send, recv, recvcount, dtype, op, comm, stream)."""
         check(lib().ncclReduceScatter(ctypes.c_void_p(send.data_ptr()), ctypes.c_void_p(recv.data_ptr()), recv.numel(),
-                                      nccl_dtype(send.dtype), NCCL_OPS[op], self.comm, stream_ptr(stream)),
+                                      nccl_dtype(send.dtype), nccl_op(op), self.comm, stream_ptr(stream)),
               "ncclReduceScatter")
         return recv
 
@@ -656,9 +681,31 @@ class Communicator:
         if recv is None and self.rank == root:
             recv = send
         check(lib().ncclReduce(ctypes.c_void_p(send.data_ptr()), ctypes.c_void_p(None if recv is None else recv.data_ptr()),
-                               send.numel(), nccl_dtype(send.dtype), NCCL_OPS[op], root, self.comm, stream_ptr(stream)),
+                               send.numel(), nccl_dtype(send.dtype), nccl_op(op), root, self.comm, stream_ptr(stream)),
               "ncclReduce")
         return recv
+
+    def create_premul_sum(self, factor, dtype):
+        """ncclRedOpCreatePreMulSum: the handle (an int, to be passed as op= of all_reduce /
+        reduce_scatter / reduce with tensors of `dtype`) of "this rank's input times `factor`, summed".
+        factor: a Python number -- rounded to `dtype` here, as a caller of the C entry point must, and
+        passed as a host immediate -- or a device tensor of `dtype`, whose first element every
+        collective that uses the handle reads when it runs (ncclScalarDevice)."""
+        h = ctypes.c_int(-1)
+        if isinstance(factor, torch.Tensor):
+            assert factor.dtype == dtype and factor.is_cuda
+            scalar, residence = ctypes.c_void_p(factor.data_ptr()), SCALAR_DEVICE
+        else:
+            raw = torch.tensor([factor], dtype=dtype).view(torch.uint8).numpy().tobytes()
+            keep = ctypes.create_string_buffer(raw, len(raw))
+            scalar, residence = ctypes.cast(keep, ctypes.c_void_p), SCALAR_HOST_IMMEDIATE
+        check(lib().ncclRedOpCreatePreMulSum(ctypes.byref(h), scalar, nccl_dtype(dtype), residence, self.comm),
+              "ncclRedOpCreatePreMulSum")
+        return h.value
+
+    def destroy_op(self, handle):
+        """ncclRedOpDestroy; legal as soon as the collective calls that used the handle have returned."""
+        check(lib().ncclRedOpDestroy(int(handle), self.comm), "ncclRedOpDestroy")
 
     def all_to_all(self, send, recv, stream=None):
         """ncclAllToAll(send, recv, count, dtype, comm, stream): block p of send lands as block rank of

@@ -460,7 +460,10 @@ ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, n
     const int o = opFromNccl(op), po = pullOpFromNccl(op);
     // int64 / uint64 / int8: every operation the pull-reduce kernel computes for them, or nothing
     const int pdt = pullOnlyDtypeFromNccl(datatype), pdo = pdt >= 0 ? pullOnlyOpFromNccl(op) : -1;
-    const bool carried = pdt >= 0 ? pdo >= 0 : dt >= 0 && (o >= 0 || po >= 0);
+    // a live PreMulSum handle of this communicator (ncclRedOpCreatePreMulSum; none with a vendor communicator)
+    ncclComm::PreMulOp pm;
+    const bool premul = comm->preMulFind(op, &pm);
+    const bool carried = premul || (pdt >= 0 ? pdo >= 0 : dt >= 0 && (o >= 0 || po >= 0));
     if (comm->fallback && (!carried || forcedFallback("allreduce")))  // nccl.cc:628-632
       return (int)vendorNccl()->AllReduce(sendbuff, recvbuff, count, datatype, op, (ncclComm_t)comm->fallback, stream);
     // every native path reads the send range (its own and, zero-copy, the peers') while receive ranges
@@ -468,6 +471,14 @@ ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, n
     if (sendbuff != recvbuff && bufferRangesOverlap(sendbuff, bytes, recvbuff, bytes)) {
       warn("ncclAllReduce: the send and receive ranges overlap without being identical");
       return (int)ncclInvalidArgument;
+    }
+    if (premul) {  // the pull-reduce kernel, this rank's scalar travelling with the launch
+      if (pm.datatype != datatype) {
+        warn("ncclAllReduce: the PreMulSum handle was created for another data type");
+        return (int)ncclInvalidArgument;
+      }
+      return comm->pullReduce(MSCCLPP_AMD_PULL_ALLREDUCE, sendbuff, recvbuff, bytes, dt, MSCCLPP_AMD_PREMUL_SUM, 0,
+                              (hipStream_t)stream, pm.scalar, pm.device);
     }
     if (pdt >= 0 && pdo >= 0)  // int64 / uint64 / int8, any of the four ops: the pull-reduce kernel
       return comm->pullReduce(MSCCLPP_AMD_PULL_ALLREDUCE, sendbuff, recvbuff, bytes, pdt, pdo, 0, (hipStream_t)stream);
@@ -496,7 +507,9 @@ ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recv
     if (!sendbuff || !recvbuff || recvcount == 0 || tb == 0) return (int)ncclInvalidArgument;
     const int dt = dtypeFromNccl(datatype), o = opFromNccl(op), po = pullOpFromNccl(op);
     const int pdt = pullOnlyDtypeFromNccl(datatype), pdo = pdt >= 0 ? pullOnlyOpFromNccl(op) : -1;  // as ncclAllReduce
-    const bool carried = pdt >= 0 ? pdo >= 0 : dt >= 0 && (o >= 0 || po >= 0);
+    ncclComm::PreMulOp pm;
+    const bool premul = comm->preMulFind(op, &pm);  // as ncclAllReduce
+    const bool carried = premul || (pdt >= 0 ? pdo >= 0 : dt >= 0 && (o >= 0 || po >= 0));
     if (comm->fallback && (!carried || forcedFallback("reducescatter")))  // nccl.cc:682-686
       return (int)vendorNccl()->ReduceScatter(sendbuff, recvbuff, recvcount, datatype, op, (ncclComm_t)comm->fallback,
                                               stream);
@@ -506,6 +519,14 @@ ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recv
     if (recvbuff != mine && bufferRangesOverlap(sendbuff, bytes * (size_t)comm->nranks, recvbuff, bytes)) {
       warn("ncclReduceScatter: the receive range overlaps the send buffer elsewhere than at its own block");
       return (int)ncclInvalidArgument;
+    }
+    if (premul) {
+      if (pm.datatype != datatype) {
+        warn("ncclReduceScatter: the PreMulSum handle was created for another data type");
+        return (int)ncclInvalidArgument;
+      }
+      return comm->pullReduce(MSCCLPP_AMD_PULL_REDUCE_SCATTER, sendbuff, recvbuff, bytes, dt, MSCCLPP_AMD_PREMUL_SUM, 0,
+                              (hipStream_t)stream, pm.scalar, pm.device);
     }
     if (pdt >= 0 && pdo >= 0)  // int64 / uint64 / int8, any of the four ops: the pull-reduce kernel
       return comm->pullReduce(MSCCLPP_AMD_PULL_REDUCE_SCATTER, sendbuff, recvbuff, bytes, pdt, pdo, 0, (hipStream_t)stream);

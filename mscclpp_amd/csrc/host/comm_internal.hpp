@@ -39,7 +39,8 @@ int launchReduce(const mscclppAmdRankView* views, int nviews, int nranks, size_t
                  int nblocks, int nthreads, uint64_t budget, hipStream_t s);
 int reduceDefaultBlocks(uint64_t bytes);
 int launchPullReduce(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes, int dtype, int op,
-                     int root, int nblocks, int nthreads, uint64_t budget, hipStream_t s);
+                     int root, int nblocks, int nthreads, uint64_t budget, hipStream_t s, const float* scales = nullptr,
+                     const void* const* scalePtrs = nullptr);
 int pullReduceDefaultBlocks(int coll, uint64_t bytes);
 int launchSendRecv(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdSendRecvOp* ops, int nops,
                    int nblocks, int nthreads, uint64_t budget, hipStream_t s);
@@ -228,6 +229,31 @@ inline int pullOnlyOpFromNccl(ncclRedOp_t op) {
   if (op == ncclSum) return MSCCLPP_AMD_SUM;
   if (op == ncclMin) return MSCCLPP_AMD_MIN;
   return pullOpFromNccl(op);
+}
+// The exact fp32 value of bf16 / fp16 bits (a PreMulSum scalar given as a host immediate).
+inline float bf16BitsToFloat(uint16_t h) {
+  const uint32_t u = (uint32_t)h << 16;
+  float f;
+  std::memcpy(&f, &u, sizeof(f));
+  return f;
+}
+inline float f16BitsToFloat(uint16_t h) {
+  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, exp = (h >> 10) & 0x1fu, man = h & 0x3ffu;
+  uint32_t u;
+  if (exp == 0x1fu) {
+    u = sign | 0x7f800000u | (man << 13);  // inf / NaN
+  } else if (exp != 0) {
+    u = sign | ((exp + 112u) << 23) | (man << 13);
+  } else if (man == 0) {
+    u = sign;
+  } else {  // subnormal: man * 2^-24, exact in fp32
+    float f = (float)man * 5.9604644775390625e-08f;
+    std::memcpy(&u, &f, sizeof(u));
+    u |= sign;
+  }
+  float f;
+  std::memcpy(&f, &u, sizeof(f));
+  return f;
 }
 inline bool bufferRangesOverlap(const void* a, size_t na, const void* b, size_t nb) {
   const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
@@ -767,7 +793,10 @@ struct ncclComm {
   // what the peers read, so it is registered on every rank; an AllReduce's peers also read this rank's reduced slice out of its receive buffer,
   // which is registered too (the same registration when in place).  bytes: the message of Reduce /
   // AllReduce, the per-rank block of ReduceScatter.  Every rank derives the same grid from (coll, bytes).
-  int pullReduce(int coll, const void* send, void* recv, size_t bytes, int dtype, int op, int root, hipStream_t stream) {
+  // op MSCCLPP_AMD_PREMUL_SUM: this rank's scalar is `scale`, or, where scalePtr is
+  // non-null, the element of the element type it points to in device memory when the kernel runs.
+  int pullReduce(int coll, const void* send, void* recv, size_t bytes, int dtype, int op, int root, hipStream_t stream,
+                 float scale = 0.0f, const void* scalePtr = nullptr) {
     std::lock_guard<std::mutex> lk(mu);
     mscclppAmdRankView v = pullView(send, recv, stream);
     if (coll == MSCCLPP_AMD_PULL_ALLREDUCE) {
@@ -778,9 +807,41 @@ struct ncclComm {
         for (int r = 0; r < nranks; ++r) v.peerOutput[r] = outs[r];
       }
     }
-    const int rc = launchPullReduce(&v, 1, nranks, coll, bytes, dtype, op, root, 0, 0, spinBudgetTicks(), stream);
+    const int rc = launchPullReduce(&v, 1, nranks, coll, bytes, dtype, op, root, 0, 0, spinBudgetTicks(), stream, &scale,
+                                    &scalePtr);
     recordUses(stream);
     return rc;
+  }
+
+  // ---- PreMulSum handles (ncclRedOpCreatePreMulSum / ncclRedOpDestroy) -----------
+  // A handle's value is ncclNumOps + its slot; a destroyed slot is taken again by the next create.
+  // With a vendor communicator the handles are the vendor library's and this table stays empty.
+  struct PreMulOp {
+    bool live = false;
+    ncclDataType_t datatype = ncclFloat32;
+    float scalar = 0.0f;          // ncclScalarHostImmediate: decoded when the handle was created
+    const void* device = nullptr;  // ncclScalarDevice: read by the kernel of every collective that uses the handle
+  };
+  std::vector<PreMulOp> preMulOps;  // under mu
+  ncclRedOp_t preMulCreate(const PreMulOp& e) {
+    std::lock_guard<std::mutex> lk(mu);
+    size_t slot = 0;
+    while (slot < preMulOps.size() && preMulOps[slot].live) ++slot;
+    if (slot == preMulOps.size()) preMulOps.emplace_back();
+    preMulOps[slot] = e;
+    preMulOps[slot].live = true;
+    return (ncclRedOp_t)((int)ncclNumOps + (int)slot);
+  }
+  // The live entry of `op` (a copy: the caller launches after the lock is dropped, and the handle may
+  // be destroyed as soon as the collective call has returned), or false.
+  bool preMulFind(ncclRedOp_t op, PreMulOp* out, bool destroy = false) {
+    const long slot = (long)(int)op - (long)ncclNumOps;
+    if (slot < 0) return false;  // a built-in operation: no lock on the path of every collective call
+    std::lock_guard<std::mutex> lk(mu);
+    if (slot >= (long)preMulOps.size() || !preMulOps[(size_t)slot].live) return false;
+    if (out) *out = preMulOps[(size_t)slot];
+    if (destroy) preMulOps[(size_t)slot].live = false;
+    return true;
   }
 
   // ---- Send / Recv by a zero-copy pull (kernels/sendrecv.hip) ------------------

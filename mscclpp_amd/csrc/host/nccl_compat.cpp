@@ -6,14 +6,19 @@
 //    to the vendor library, nccl.cc:794-821), ncclReduce (zero-copy pull-reduce at the root,
 //    kernels/reduce.hip, for the data types and operations AllReduce carries -- ncclMax / ncclAvg and
 //    every operation of int64 / uint64 / int8 by kernels/pull_reduce.hip; the reference returns
-//    ncclInternalError without a vendor library, nccl.cc:521-542), ncclSend / ncclRecv between two
+//    ncclInternalError without a vendor library, nccl.cc:521-542), ncclRedOpCreatePreMulSum /
+//    ncclRedOpDestroy for fp16 / bf16 / fp32 on a communicator without a vendor one (a handle table
+//    per communicator; AllReduce / ReduceScatter / Reduce with a live handle take the same kernel,
+//    which exchanges the ranks' scalars itself; with a vendor communicator both calls, and the
+//    handles, stay the vendor library's), ncclSend / ncclRecv between two
 //    different ranks, alone or inside ncclGroupStart / ncclGroupEnd (zero-copy pull by the receiver,
 //    kernels/sendrecv.hip; the reference: nccl.cc:774-792), ncclCommSplit (nccl.cc:405-435),
 //    ncclCommInitRankScalable with one id, ncclCommRegister / Deregister and ncclCommWindowRegister /
 //    Deregister (the path registers buffers lazily on first use, so these only hand the pointer back);
 //  * forwarded to the vendor library when MSCCLPP_AMD_NCCL_LIB_PATH (or the reference's
 //    MSCCLPP_NCCL_LIB_PATH) names it -- the reference's dlopen fallback, nccl.cc:72-160, :323-346:
-//    ncclSend/Recv to oneself, ncclRedOpCreatePreMulSum/Destroy, ncclGroupSimulateEnd, group calls
+//    ncclSend/Recv to oneself, ncclRedOpCreatePreMulSum/Destroy (of a communicator that has a vendor
+//    one; natively otherwise, see above), ncclGroupSimulateEnd, group calls
 //    (beside the native group queue), and AllReduce / AllGather / ReduceScatter / Broadcast /
 //    AllToAll(v) / Reduce / Send / Recv for data types and operations this path does not carry or
 //    that MSCCLPP_AMD_FORCE_NCCL_FALLBACK_OPERATION (reference:
@@ -380,9 +385,19 @@ ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, nccl
     }
     const int dt = dtypeFromNccl(datatype), o = opFromNccl(op), po = pullOpFromNccl(op);
     const int pdt = pullOnlyDtypeFromNccl(datatype), pdo = pdt >= 0 ? pullOnlyOpFromNccl(op) : -1;  // as ncclAllReduce
-    const bool carried = pdt >= 0 ? pdo >= 0 : dt >= 0 && (o >= 0 || po >= 0);
+    ncclComm::PreMulOp pm;
+    const bool premul = comm->preMulFind(op, &pm);  // as ncclAllReduce
+    const bool carried = premul || (pdt >= 0 ? pdo >= 0 : dt >= 0 && (o >= 0 || po >= 0));
     if (vendorComm(comm) && vendorNccl()->Reduce && (!carried || forcedFallback("reduce")))
       return (int)vendorNccl()->Reduce(sendbuff, recvbuff, count, datatype, op, root, vendorComm(comm), stream);
+    if (premul) {
+      if (pm.datatype != datatype) {
+        warn("ncclReduce: the PreMulSum handle was created for another data type");
+        return (int)ncclInvalidArgument;
+      }
+      return comm->pullReduce(MSCCLPP_AMD_PULL_REDUCE, sendbuff, isRoot ? recvbuff : nullptr, bytes, dt,
+                              MSCCLPP_AMD_PREMUL_SUM, root, (hipStream_t)stream, pm.scalar, pm.device);
+    }
     if (pdt >= 0 && pdo >= 0)  // int64 / uint64 / int8, any of the four ops: the pull-reduce kernel
       return comm->pullReduce(MSCCLPP_AMD_PULL_REDUCE, sendbuff, isRoot ? recvbuff : nullptr, bytes, pdt, pdo, root,
                               (hipStream_t)stream);
@@ -531,12 +546,37 @@ ncclResult_t ncclRedOpCreatePreMulSum(ncclRedOp_t* op, void* scalar, ncclDataTyp
                                       ncclScalarResidence_t residence, ncclComm_t comm) {
   if (vendorComm(comm) && vendorNccl()->RedOpCreatePreMulSum)
     return vendorNccl()->RedOpCreatePreMulSum(op, scalar, datatype, residence, vendorComm(comm));
-  return unavailable("ncclRedOpCreatePreMulSum");
+  // native (kernels/pull_reduce.hip): a handle of this communicator's own table
+  return (ncclResult_t)guarded([&] {
+    if (!op || !scalar || !comm) return (int)ncclInvalidArgument;
+    if (residence != ncclScalarDevice && residence != ncclScalarHostImmediate) return (int)ncclInvalidArgument;
+    if (datatype != ncclFloat16 && datatype != ncclBfloat16 && datatype != ncclFloat32)
+      return (int)unavailable("ncclRedOpCreatePreMulSum of this data type");
+    if (comm->nranks == 1)  // x * s alone, which no kernel here computes
+      return (int)unavailable("ncclRedOpCreatePreMulSum on a one-rank communicator");
+    ncclComm::PreMulOp e;
+    e.datatype = datatype;
+    if (residence == ncclScalarDevice) {
+      e.device = scalar;
+    } else if (datatype == ncclFloat32) {
+      std::memcpy(&e.scalar, scalar, sizeof(float));
+    } else {  // the element's bits, decoded exactly
+      uint16_t h = 0;
+      std::memcpy(&h, scalar, sizeof(h));
+      e.scalar = datatype == ncclBfloat16 ? bf16BitsToFloat(h) : f16BitsToFloat(h);
+    }
+    *op = comm->preMulCreate(e);
+    return (int)ncclSuccess;
+  });
 }
 
 ncclResult_t ncclRedOpDestroy(ncclRedOp_t op, ncclComm_t comm) {
   if (vendorComm(comm) && vendorNccl()->RedOpDestroy) return vendorNccl()->RedOpDestroy(op, vendorComm(comm));
-  return unavailable("ncclRedOpDestroy");
+  // (the launches that used the handle carry its scalar, or its pointer, in their arguments)
+  return (ncclResult_t)guarded([&] {
+    if (!comm || !comm->preMulFind(op, nullptr, /*destroy=*/true)) return (int)ncclInvalidArgument;
+    return (int)ncclSuccess;
+  });
 }
 
 ncclResult_t ncclGroupSimulateEnd(ncclSimInfo_t* simInfo) {
@@ -669,8 +709,10 @@ int mscclppAmdSendRecvDefaultBlocks(uint64_t bytes) { return mscclpp_amd::sendre
 // ncclMax / ncclAvg of Reduce / ReduceScatter / AllReduce, and the four operations of int64 / uint64 /
 // int8, for in-process ranks (and the one-view form the NCCL entry points launch): everything is
 // checked before a device is touched; a refusal launches nothing.
-int mscclppAmdPullReduceLaunch(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes, int dtype,
-                               int op, int root, int nblocks, int nthreads, uint64_t budgetTicks, void* stream) {
+// `scaled`: mscclppAmdPullReduceLaunchScaled, which takes PreMulSum (with its scalars) and nothing else.
+static int pullReduceLaunch(bool scaled, const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes,
+                            int dtype, int op, int root, int nblocks, int nthreads, uint64_t budgetTicks, void* stream,
+                            const float* scales, const void* const* scalePtrs) {
   return guarded([&] {
     if (coll < MSCCLPP_AMD_PULL_REDUCE || coll > MSCCLPP_AMD_PULL_ALLREDUCE) return (int)ncclInvalidArgument;
     const bool reduce = coll == MSCCLPP_AMD_PULL_REDUCE, all = coll == MSCCLPP_AMD_PULL_ALLREDUCE;
@@ -678,7 +720,11 @@ int mscclppAmdPullReduceLaunch(const mscclppAmdRankView* views, int nviews, int 
     // SUM / MIN of the eight types that have their own kernels for them are refused; of int64 / uint64 /
     // int8, which have no other kernel, they are taken
     const bool pullOnly = dtype == MSCCLPP_AMD_I64 || dtype == MSCCLPP_AMD_U64 || dtype == MSCCLPP_AMD_I8;
-    if (op != MSCCLPP_AMD_MAX && op != MSCCLPP_AMD_AVG && !(pullOnly && (op == MSCCLPP_AMD_SUM || op == MSCCLPP_AMD_MIN)))
+    if (scaled) {
+      const bool floats = dtype == MSCCLPP_AMD_F16 || dtype == MSCCLPP_AMD_BF16 || dtype == MSCCLPP_AMD_F32;
+      if (op != MSCCLPP_AMD_PREMUL_SUM || !floats || !scales) return (int)ncclInvalidArgument;
+    } else if (op != MSCCLPP_AMD_MAX && op != MSCCLPP_AMD_AVG &&
+               !(pullOnly && (op == MSCCLPP_AMD_SUM || op == MSCCLPP_AMD_MIN)))
       return (int)ncclInvalidArgument;
     if (bytes == 0) return (int)ncclInvalidArgument;  // (the dtype codes and a split element: launchPullReduce)
     // what moves data: every view, but for Reduce the root's alone (the others read and write no user memory)
@@ -693,8 +739,23 @@ int mscclppAmdPullReduceLaunch(const mscclppAmdRankView* views, int nviews, int 
       seen |= 1u << views[i].rank;
     }
     return mscclpp_amd::launchPullReduce(views, nviews, nranks, coll, bytes, dtype, op, root, nblocks, nthreads,
-                                         budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream);
+                                         budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream,
+                                         scaled ? scales : nullptr, scaled ? scalePtrs : nullptr);
   });
+}
+
+int mscclppAmdPullReduceLaunch(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes, int dtype,
+                               int op, int root, int nblocks, int nthreads, uint64_t budgetTicks, void* stream) {
+  return pullReduceLaunch(false, views, nviews, nranks, coll, bytes, dtype, op, root, nblocks, nthreads, budgetTicks,
+                          stream, nullptr, nullptr);
+}
+
+// PreMulSum for in-process ranks (and the one-view form): scales[i] / scalePtrs[i] belong to views[i].
+int mscclppAmdPullReduceLaunchScaled(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes,
+                                     int dtype, int op, int root, int nblocks, int nthreads, uint64_t budgetTicks,
+                                     void* stream, const float* scales, const void* const* scalePtrs) {
+  return pullReduceLaunch(true, views, nviews, nranks, coll, bytes, dtype, op, root, nblocks, nthreads, budgetTicks,
+                          stream, scales, scalePtrs);
 }
 
 int mscclppAmdPullReduceDefaultBlocks(int coll, uint64_t bytes) { return mscclpp_amd::pullReduceDefaultBlocks(coll, bytes); }

@@ -1,5 +1,6 @@
-// ncclMax / ncclAvg for Reduce, ReduceScatter and AllReduce, and SUM / MIN / MAX / AVG of int64, uint64
-// and int8: one zero-copy pull-reduce kernel.
+// ncclMax / ncclAvg for Reduce, ReduceScatter and AllReduce, SUM / MIN / MAX / AVG of int64, uint64
+// and int8, and PreMulSum (ncclRedOpCreatePreMulSum) of fp16 / bf16 / fp32: one zero-copy pull-reduce
+// kernel.
 //
 // The reference carries SUM and MIN of fp16, bf16, fp32, int32, uint32, uint8 and fp8 (and leaves the
 // other operations and types to the vendor library), so
@@ -34,6 +35,21 @@
 //    (pull_acc_words).  A range that ends on an odd 64-bit element has an 8-byte tail, moved byte by
 //    byte like any other; the zero-filled rest of that unit is reduced and not stored.
 //  * Exit handshake: every reader is done with this rank's send and receive buffers.
+//  * PreMulSum only: every rank has a scalar of its own, and the rank that reduces a range needs
+//    every rank's.  They are exchanged inside the kernel, per workgroup, through the DIAGONAL of the
+//    token arrays: slot [rank][b] of a rank's own array, which no handshake touches (a rank never
+//    signals itself), which every peer has mapped already (peerTokens[rank]), and which is uncached
+//    memory.  Lane 0 of workgroup b (also one whose share is empty) stores its view's scalar there --
+//    the fp32 bits in the 64-bit word, a system-scope store -- before the entry handshake, whose drain,
+//    barrier and release publish it with the token add; after the handshake's acquire lane k < n of
+//    every wave reads rank k's slot with a system-scope load (one round trip for all n) and the wave
+//    reads the values out lane by lane (v_readlane): they are uniform and cost SGPRs, not VGPRs.
+//    Every peer reads them before it enters any later handshake, so after the exit handshake no
+//    reader is left and lane 0 stores 0 back: a token array equals its expected counters after every
+//    launch, as before.  The next launch of the rank on the stream publishes after this one's end.
+//    The scalar is an immediate in the kernel arguments, or is read by lane 0 through a device
+//    pointer to one element of the element type when the kernel runs (a graph replay sees the value
+//    of its own time).
 //  * Tails and alignment as reduce.hip: the last unit of a range that is no multiple of 16 bytes
 //    moves byte by byte; no byte outside [recv + dstOff, + len) is written and none outside a send
 //    buffer's extent is read.  Pointers need their element's alignment only and the misalignment
@@ -43,11 +59,14 @@
 #include "launch.hpp"
 #include "mscclpp_amd/pull_reduce_device.hpp"
 
+#include <type_traits>
+
 namespace mscclpp_amd {
 
-// Units per lane in flight, from the resource report of the 56 instantiations (hipcc
-// -Rpass-analysis=kernel-resource-usage; DESIGN.md §17d and §17e have the tables; none uses scratch,
-// and the 64-bit AVG stays at 96 VGPRs with U = 2, so no instantiation needs a U of its own).  As for
+// Units per lane in flight, from the resource report of the 62 instantiations (hipcc
+// -Rpass-analysis=kernel-resource-usage; DESIGN.md §17d, §17e and §17f have the tables; none uses
+// scratch, the 64-bit AVG stays at 96 VGPRs and PreMulSum at 92 with U = 2, so no instantiation needs
+// a U of its own).  As for
 // reduceKernel, U = 2 keeps 256 bytes of loads per lane in flight at 8 ranks and stays at or below
 // 128 VGPRs, i.e. two 512-lane workgroups per CU, which the in-process launch of 8 ranks x 64
 // workgroups needs to be resident at once.
@@ -66,15 +85,46 @@ struct PullReduceArgs {
   int nranks;
   int gather;       // AllReduce: phase 2 copies the peers' reduced slices
 };
-static_assert(sizeof(PullReduceArgs<kMaxRanks>) <= 4096, "in-process pull-reduce arguments exceed the kernel-argument limit");
+// PreMulSum's arguments: the same and a scalar per view.  A type of its own, because a longer
+// argument block moves the implicit arguments behind it (the block size is read from there) and so
+// changes the code of every kernel that takes it: the other operations keep theirs to the byte.
+template <int NV>
+struct PullPreMulArgs : PullReduceArgs<NV> {
+  float scale[NV];            // the rank's scalar, unless ...
+  const void* scalePtr[NV];   // ... non-null: one element of the element type in device memory, read by the kernel
+};
+static_assert(sizeof(PullPreMulArgs<kMaxRanks>) <= 4096, "in-process pull-reduce arguments exceed the kernel-argument limit");
+
+template <int OP, int NV>
+using PullArgsFor = std::conditional_t<OP == kPullPreMulSum, PullPreMulArgs<NV>, PullReduceArgs<NV>>;
 
 template <int DT, int OP, int NV, int U>
-__global__ void __launch_bounds__(512) pullReduceKernel(PullReduceArgs<NV> a) {
+__global__ void __launch_bounds__(512) pullReduceKernel(PullArgsFor<OP, NV> a) {
   const mscclppAmdRankView& v = a.views.v[NV == 1 ? 0 : blockIdx.y];
   const int rank = v.rank, n = a.nranks;
   const uint32_t T = blockDim.x, tid = threadIdx.x, b = blockIdx.x;
   trace_stamp(a.trace, 0);
+  [[maybe_unused]] float sc[kMaxRanks];  // PreMulSum: rank k's scalar
+  if constexpr (OP == kPullPreMulSum) {
+    if (tid == 0) {
+      const uint32_t vi = NV == 1 ? 0 : blockIdx.y;
+      const float s = a.scalePtr[vi] ? premul_scalar_at<DT>(a.scalePtr[vi]) : a.scale[vi];
+      st_relaxed_sys(v.tokens + (uint64_t)rank * kMaxChannels + b, (uint64_t)__builtin_bit_cast(uint32_t, s));
+    }
+  }
   block_handshake(v, n, rank, b, a.budget);
+  if constexpr (OP == kPullPreMulSum) {
+    // lane k < n of every wave loads rank k's slot (one round trip for all of them), and the values
+    // are then read out of its register lane by lane: uniform, so they cost SGPRs, not VGPRs
+    const int lane = (int)(tid & 63u);
+    uint32_t got = 0;
+    if (lane < n) {
+      const uint64_t* slot = (lane == rank ? v.tokens : v.peerTokens[lane]) + (uint64_t)lane * kMaxChannels + b;
+      got = (uint32_t)ld_relaxed_sys(slot);
+    }
+#pragma unroll
+    for (int k = 0; k < kMaxRanks; ++k) sc[k] = __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_readlane((int)got, k));
+  }
   trace_stamp(a.trace, 1);
   const uint64_t bOff = (uint64_t)b * a.blk;
   if (bOff < a.len[rank]) {
@@ -127,10 +177,17 @@ __global__ void __launch_bounds__(512) pullReduceKernel(PullReduceArgs<NV> a) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             PullAcc<DT, OP> acc;
-            acc.first(w[i][0][j]);
+            if constexpr (OP == kPullPreMulSum) {
+              acc.first(w[i][0][j], sc[0]);
 #pragma unroll
-            for (int k = 1; k < kMaxRanks; ++k)
-              if (k < n) acc.next(w[i][k][j]);
+              for (int k = 1; k < kMaxRanks; ++k)
+                if (k < n) acc.next(w[i][k][j], sc[k]);
+            } else {
+              acc.first(w[i][0][j]);
+#pragma unroll
+              for (int k = 1; k < kMaxRanks; ++k)
+                if (k < n) acc.next(w[i][k][j]);
+            }
             r[j] = acc.word(n, a.invN);
           }
         }
@@ -170,8 +227,12 @@ __global__ void __launch_bounds__(512) pullReduceKernel(PullReduceArgs<NV> a) {
     trace_stamp(a.trace, 3);
   }
   block_handshake(v, n, rank, b, a.budget);
+  if constexpr (OP == kPullPreMulSum) {  // every peer has read the scalar: the slot is 0 again
+    if (tid == 0) st_relaxed_sys(v.tokens + (uint64_t)rank * kMaxChannels + b, 0);
+  }
   trace_stamp(a.trace, 4);
 }
+
 
 int reduceDefaultBlocks(uint64_t bytes);  // reduce.hip
 
@@ -217,18 +278,26 @@ uint64_t pullReduceGeometry(int coll, int nranks, uint64_t bytes, int root, uint
 
 template <int DT, int OP>
 static int launchPullReduceT(const mscclppAmdRankView* views, int nviews, int nranks, int coll, uint64_t bytes, int root,
-                             uint64_t blk, int nblocks, int nthreads, uint64_t budget, hipStream_t s) {
+                             uint64_t blk, int nblocks, int nthreads, uint64_t budget, hipStream_t s,
+                             const float* scales = nullptr, const void* const* scalePtrs = nullptr) {
+  auto fill = [&](auto& args) {
+    pullReduceGeometry(coll, nranks, bytes, root, args.srcOff, args.dstOff, args.len);
+    args.blk = blk;
+    args.budget = budget;
+    args.trace = g_mscclppAmdTrace;
+    args.invN = 1.0f / (float)nranks;
+    args.nranks = nranks;
+    args.gather = coll == MSCCLPP_AMD_PULL_ALLREDUCE;
+    if constexpr (OP == kPullPreMulSum) {
+      for (int i = 0; i < nviews; ++i) {
+        args.scale[i] = scales[i];
+        args.scalePtr[i] = scalePtrs ? scalePtrs[i] : nullptr;
+      }
+    }
+    return 0;
+  };
   return launchViews(pullReduceKernel<DT, OP, 1, kPullReduceUnits>, pullReduceKernel<DT, OP, kMaxRanks, kPullReduceUnits>,
-                     views, nviews, nblocks, nthreads, s, [&](auto& args) {
-                       pullReduceGeometry(coll, nranks, bytes, root, args.srcOff, args.dstOff, args.len);
-                       args.blk = blk;
-                       args.budget = budget;
-                       args.trace = g_mscclppAmdTrace;
-                       args.invN = 1.0f / (float)nranks;
-                       args.nranks = nranks;
-                       args.gather = coll == MSCCLPP_AMD_PULL_ALLREDUCE;
-                       return 0;
-                     });
+                     views, nviews, nblocks, nthreads, s, fill);
 }
 
 #define MSCCLPP_AMD_PULL_CASE2(DT, ...)                                            \
@@ -240,18 +309,29 @@ static int launchPullReduceT(const mscclppAmdRankView* views, int nviews, int nr
   case DT * 4 + kMin: return launchPullReduceT<DT, kMin>(__VA_ARGS__);             \
   MSCCLPP_AMD_PULL_CASE2(DT, __VA_ARGS__)
 
+// scales / scalePtrs (host arrays, one entry per view): PreMulSum only, which is refused without scales.
 int launchPullReduce(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes, int dtype, int op,
-                     int root, int nblocks, int nthreads, uint64_t budget, hipStream_t s) {
+                     int root, int nblocks, int nthreads, uint64_t budget, hipStream_t s, const float* scales,
+                     const void* const* scalePtrs) {
   if (coll < MSCCLPP_AMD_PULL_REDUCE || coll > MSCCLPP_AMD_PULL_ALLREDUCE) return 4;
   if (nblocks <= 0) nblocks = pullReduceDefaultBlocks(coll, bytes);
   if (!launchShapeOk(nblocks, kMaxChannels, nthreads)) return 4;
   if (nranks < 2 || nranks > kMaxRanks || bytes == 0) return 4;
   if (coll == MSCCLPP_AMD_PULL_REDUCE && (root < 0 || root >= nranks)) return 4;
   if (!pull_reduce_takes(dtype, op) || bytes % (size_t)elem_bytes(dtype)) return 4;
+  if (op == kPullPreMulSum && !scales) return 4;
   uint64_t srcOff[kMaxRanks], dstOff[kMaxRanks], len[kMaxRanks];
   const uint64_t most = pullReduceGeometry(coll, nranks, bytes, root, srcOff, dstOff, len);
   const uint64_t blk = blockBytes(most, (uint32_t)nblocks);
   if (blk > kBlkOffsetLimit) return 5;  // more workgroups needed: one workgroup's range is one descriptor
+  if (op == kPullPreMulSum) {  // outside the table below, whose index dtype * 4 + op it would alias
+    switch (dtype) {
+      case kF16: return launchPullReduceT<kF16, kPullPreMulSum>(views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s, scales, scalePtrs);
+      case kBF16: return launchPullReduceT<kBF16, kPullPreMulSum>(views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s, scales, scalePtrs);
+      case kF32: return launchPullReduceT<kF32, kPullPreMulSum>(views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s, scales, scalePtrs);
+      default: return 4;
+    }
+  }
   switch (dtype * 4 + op) {
     MSCCLPP_AMD_PULL_CASE2(kF16, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)
     MSCCLPP_AMD_PULL_CASE2(kBF16, views, nviews, nranks, coll, (uint64_t)bytes, root, blk, nblocks, nthreads, budget, s)

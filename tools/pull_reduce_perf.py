@@ -21,6 +21,9 @@ TYPES=int64 runs another, shorter programme instead: int64 SUM and AVG (DESIGN.m
 at the same byte counts, default grids, the three collectives, alternating in the same run; SIZES
 defaults to 8 bytes, 1 MiB and 48 MiB (a ReduceScatter needs n elements), and the result goes to
 profiles/int_reduce_perf_inprocess_n8.json.
+
+TYPES=premul: PreMulSum beside AVG of the same type and collective, fp16 / bf16 / fp32,
+SIZES 64 KiB, 1 MiB and 48 MiB by default; the result goes to profiles/premul_sum_perf_inprocess_n8.json.
 """
 import json
 import os
@@ -132,8 +135,87 @@ def int64_programme():
     json.dump(res, open(out, "w"), indent=1)
 
 
+def premul_programme():
+    """PreMulSum beside AVG of the same type and collective, alternating in the same
+    run, default grids: AVG is the yardstick (the same loads, stores and handshakes; PreMulSum adds a
+    multiply per operand and the scalar exchange: one 8-byte store and one 8-byte load of n slots per
+    wave).  Per-rank scalars as immediates, and once more read through device pointers."""
+    sizes = [int(s) for s in os.environ.get("SIZES", f"{64 << 10},{1 << 20},{48 << 20}").split(",")]
+    scal = [1.0, -0.5, 0.25, 0.75, -0.125, 0.5, 0.375, -0.25][:N]  # exact in fp16 / bf16 / fp32
+    rows = []
+    for tdt in (torch.float16, torch.bfloat16, torch.float32):
+        es = torch.empty(0, dtype=tdt).element_size()
+        for S in sizes:
+            count, blk = S // es, S // es // N
+            ranks = m.InProcessRanks(N, 1 << 16)
+            sends = [torch.rand(count, dtype=torch.float32, device=dev).to(tdt) for _ in range(N)]
+            full = [torch.zeros(count, dtype=tdt, device=dev) for _ in range(N)]
+            part = [torch.zeros(blk, dtype=tdt, device=dev) for _ in range(N)]
+            outs = {m.PULL_ALLREDUCE: full, m.PULL_REDUCE_SCATTER: part,
+                    m.PULL_REDUCE: [full[r] if r == ROOT_RANK else None for r in range(N)]}
+            ins = {c: ([t[:blk * N] for t in sends] if c == m.PULL_REDUCE_SCATTER else sends) for _, c in COLLS}
+            ptrs = [torch.tensor([s], dtype=tdt, device=dev) for s in scal]
+
+            def avg(coll):
+                ranks.pull_reduce(coll, ins[coll], outs[coll], m.AVG, root=ROOT_RANK, budget_ticks=BUDGET, stream=cur())
+
+            def premul(coll, device=False):
+                ranks.pull_reduce(coll, ins[coll], outs[coll], m.PREMUL_SUM, root=ROOT_RANK, budget_ticks=BUDGET,
+                                  stream=cur(), scales=scal, scale_tensors=ptrs if device else None)
+
+            # correctness of what is timed: fp32 products and sum in rank order, rounded once
+            want = sends[0].float() * scal[0]
+            for k in range(1, N):
+                want = want + sends[k].float() * scal[k]
+            want = want.to(tdt)
+            for _, c in COLLS:
+                premul(c, device=(c == m.PULL_REDUCE))
+            torch.cuda.synchronize()
+            ok = all(torch.equal(t, want) for t in full)
+            ok = ok and all(torch.equal(part[r], want[r * blk:(r + 1) * blk]) for r in range(N))
+            ok = ok and ranks.errors() == [0] * N
+            calls, replays = (10, 5) if S >= (8 << 20) else (50, 10)
+            lines = []
+            for name, c in COLLS:
+                lines += [("avg_" + name, (lambda c=c: avg(c))), ("premul_" + name, (lambda c=c: premul(c)))]
+            lines.append(("premul_allreduce_device_scalars", lambda: premul(m.PULL_ALLREDUCE, device=True)))
+            t = {name: [] for name, _ in lines}
+            for _ in range(ROUNDS):
+                for name, fn in lines:
+                    t[name].append(graph_us(fn, calls, replays))
+            row = {"dtype": str(tdt).replace("torch.", ""), "send_bytes_per_rank": S, "root": ROOT_RANK, "correct": bool(ok),
+                   "graph_calls": calls, "replays": replays, "rounds": ROUNDS,
+                   "default_nblocks": {name: m.lib().mscclppAmdPullReduceDefaultBlocks(c, blk * es if c == m.PULL_REDUCE_SCATTER else S)
+                                       for name, c in COLLS},
+                   "lines": {name: stat(v) for name, v in t.items()}}
+            row["premul_over_avg"] = {name: round(row["lines"]["premul_" + name]["us"] / row["lines"]["avg_" + name]["us"], 3)
+                                      for name, _ in COLLS}
+            phases = {}
+            for label, fn in (("avg", lambda: avg(m.PULL_ALLREDUCE)), ("premul", lambda: premul(m.PULL_ALLREDUCE))):
+                with m.PhaseTrace() as tr:
+                    fn()
+                    torch.cuda.synchronize()
+                phases[label] = tr.phases("pull_allreduce", view=ROOT_RANK)
+            row["phases_allreduce"] = phases
+            row["errors"] = ranks.errors()
+            rows.append(row)
+            print(row, flush=True)
+            del sends, full, part, outs, ins, ranks
+    res = {"tool": "tools/pull_reduce_perf.py TYPES=premul", "fabric_free": True, "gpus": 1, "nranks": N, "scalars": scal,
+           "note": "in-process ranks on one GPU: no xGMI byte is priced, so neither is the scalar exchange over a link; "
+                   "graph-captured, median of rounds; AVG of the same type and collective from the same run is the yardstick",
+           "rows": rows}
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = os.environ.get("OUT", os.path.join(root, "profiles", f"premul_sum_perf_inprocess_n{N}.json"))
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    json.dump(res, open(out, "w"), indent=1)
+
+
 if os.environ.get("TYPES") == "int64":
     int64_programme()
+    sys.exit(0)
+if os.environ.get("TYPES") == "premul":
+    premul_programme()
     sys.exit(0)
 
 
