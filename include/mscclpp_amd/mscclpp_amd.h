@@ -255,6 +255,33 @@ int mscclppAmdPullReduceLaunchScaled(const mscclppAmdRankView* views, int nviews
                                      int dtype, int op, int root, int nblocks, int nthreads, uint64_t budgetTicks,
                                      void* stream, const float* scales, const void* const* scalePtrs);
 int mscclppAmdPullReduceDefaultBlocks(int coll, uint64_t bytes);
+/* The same reductions for SMALL messages by one hop of LL8 packets (kernels/pull_reduce_ll.hip; DESIGN.md
+ * §17g): coll MSCCLPP_AMD_PULL_REDUCE_SCATTER or _ALLREDUCE only (a Reduce keeps the pull kernel: only
+ * its root would wait for packets, which the reuse of the two scratch halves forbids), every (dtype,
+ * op) mscclppAmdPullReduceLaunch / ...LaunchScaled take, operands in the same rank order, so the bits
+ * are those of the pull path.  Views as for mscclppAmdAllReduceLaunch with MSCCLPP_AMD_ALGO_ALLPAIR
+ * (input, output, scratch, peerScratch[q], flags, err; no tokens, no peerInput: no user buffer is read by
+ * a peer and no handshake runs); the flags and the scratch are shared with the LL AllReduce kernels.
+ * In place is carried as input == output (AllReduce) and output == input + rank * bytes
+ * (ReduceScatter).  scales / scalePtrs: as for mscclppAmdPullReduceLaunchScaled with op
+ * MSCCLPP_AMD_PREMUL_SUM, NULL for every other op.  nblocks / nthreads <= 0: one lane per 8 payload
+ * bytes, 256 lanes, up to 128 workgroups -- a function of `bytes` alone.
+ * 4 (nothing is launched, no device is touched): coll MSCCLPP_AMD_PULL_REDUCE or any other code, a
+ * (dtype, op) the pull path refuses, a byte count of 0 or one that splits an element, nranks outside
+ * 2..8, scales without PREMUL_SUM or PREMUL_SUM without scales, a bad launch shape, null fields;
+ * 5: views whose scratchBytes differ or are below mscclppAmdPullReduceLLScratchRequired, a size the
+ * path does not carry, or a grid that cannot be resident at once. */
+int mscclppAmdPullReduceLLLaunch(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes,
+                                 int dtype, int op, int nblocks, int nthreads, uint64_t budgetTicks, void* stream,
+                                 const float* scales, const void* const* scalePtrs);
+/* Scratch bytes per rank that call needs (two halves of nranks regions of ceil(words / 2) 16-byte
+ * units, plus one unit per region for PREMUL_SUM's scalar); 0: the call is not carried. */
+size_t mscclppAmdPullReduceLLScratchRequired(int coll, int nranks, size_t bytes, int dtype, int op);
+/* 1 when ncclAllReduce / ncclReduceScatter send a call of `bytes` (the message / the per-rank block) of
+ * these operations to the LL path, else 0: bytes <= the built-in bound of (coll, nranks) (DESIGN.md
+ * §17g), or <= MSCCLPP_AMD_PULL_LL_MAX_BYTES where that is set (one bound for both collectives, 0
+ * disables the path, values above 1 MiB count as 1 MiB; read once; it must be equal on all ranks). */
+int mscclppAmdPullReduceTakesLL(int coll, int nranks, size_t bytes);
 /* Send / Recv by a zero-copy pull (kernels/sendrecv.hip): one launch runs a table of point-to-point
  * operations, in table order.  An operation moves `bytes` from `send` on rank `src` to `recv` on
  * rank `dst`: the receiver reads `send` -- the address at which the view of rank `dst` has the
@@ -354,6 +381,8 @@ int mscclppAmdCommRegistrationStats(ncclComm_t comm, size_t* userRegistrations, 
  * MSCCLPP_NCCL_SYMMETRIC_MEMORY, env.hpp:101-107, which *symmetricMemory reports). */
 int mscclppAmdCommRegistrationExchanges(ncclComm_t comm, uint64_t* allocationExchanges, uint64_t* offsetExchanges,
                                         int* symmetricMemory);
+/* Collective calls of this communicator that took the LL path of mscclppAmdPullReduceLLLaunch. */
+int mscclppAmdCommPullLLCount(ncclComm_t comm, uint64_t* count);
 int mscclppAmdCommScratch(ncclComm_t comm, void** scratch, size_t* bytes);
 int mscclppAmdCommFlags(ncclComm_t comm, uint32_t** flags);
 /* Bootstrap all-gather of `bytes` per rank (host memory), for harnesses. */

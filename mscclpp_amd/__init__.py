@@ -173,6 +173,10 @@ def lib():
         "mscclppAmdPullReduceLaunchScaled": [ctypes.POINTER(RankView), i32, i32, i32, sz, i32, i32, i32, i32, i32, u64, vp,
                                              ctypes.POINTER(ctypes.c_float), ctypes.POINTER(vp)],
         "mscclppAmdPullReduceDefaultBlocks": [i32, u64],
+        "mscclppAmdPullReduceLLLaunch": [ctypes.POINTER(RankView), i32, i32, i32, sz, i32, i32, i32, i32, u64, vp,
+                                         ctypes.POINTER(ctypes.c_float), ctypes.POINTER(vp)],
+        "mscclppAmdPullReduceTakesLL": [i32, i32, sz],
+        "mscclppAmdCommPullLLCount": [vp, ctypes.POINTER(ctypes.c_uint64)],
         "ncclRedOpCreatePreMulSum": [ctypes.POINTER(i32), vp, i32, i32, vp],
         "ncclRedOpDestroy": [i32, vp],
         "mscclppAmdSendRecvLaunch": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(SendRecvOp), i32, i32, i32, u64, vp],
@@ -222,6 +226,8 @@ def lib():
         f.restype = ctypes.c_int
     L.mscclppAmdScratchRequired.argtypes = [i32, i32, sz, i32]
     L.mscclppAmdScratchRequired.restype = sz
+    L.mscclppAmdPullReduceLLScratchRequired.argtypes = [i32, i32, sz, i32, i32]
+    L.mscclppAmdPullReduceLLScratchRequired.restype = sz
     for name in ("mscclppAmdExecutionPlanName", "mscclppAmdExecutionPlanCollective"):
         getattr(L, name).argtypes = [vp]
         getattr(L, name).restype = ctypes.c_char_p
@@ -367,6 +373,7 @@ TRACE_PHASES = {
     "sendrecv": ("post_ready", "pull", "wait_done"),
     "pull_reduce": ("entry_handshake", "pull_reduce", "exit_handshake"),
     "pull_allreduce": ("entry_handshake", "pull_reduce", "gather", "exit_handshake"),
+    "pull_reduce_ll": ("put", "reduce"),
 }
 
 
@@ -418,6 +425,18 @@ class PhaseTrace:
 
 def scratch_required(algo, nranks, nbytes, dtype_code):
     return lib().mscclppAmdScratchRequired(algo, nranks, nbytes, dtype_code)
+
+
+def pull_reduce_takes_ll(coll, nranks, nbytes):
+    """Whether ncclAllReduce / ncclReduceScatter send a MAX / AVG / int64 / uint64 / int8 / PreMulSum call of
+    nbytes (the message, or the per-rank block of a ReduceScatter) to the LL path: the built-in bound of
+    (coll, nranks), or MSCCLPP_AMD_PULL_LL_MAX_BYTES."""
+    return bool(lib().mscclppAmdPullReduceTakesLL(coll, nranks, nbytes))
+
+
+def pull_reduce_ll_scratch_required(coll, nranks, nbytes, dtype_code, op):
+    """Scratch bytes per rank InProcessRanks.pull_reduce_ll needs for that call; 0: not carried."""
+    return lib().mscclppAmdPullReduceLLScratchRequired(coll, nranks, nbytes, dtype_code, op)
 
 
 class InProcessRanks:
@@ -561,6 +580,23 @@ class InProcessRanks:
             code = lib().mscclppAmdPullReduceLaunchScaled(arr, self.n, self.n, coll, nbytes, dt, op, root, nblocks,
                                                           nthreads, budget_ticks, stream_ptr(stream), imm, ptrs)
         check(code, "in-process pull_reduce")
+
+    def pull_reduce_ll(self, coll, inputs, outputs, op, nblocks=0, nthreads=0, budget_ticks=500_000_000, stream=None,
+                       accum=None, scales=None, scale_tensors=None):
+        """pull_reduce's PULL_REDUCE_SCATTER / PULL_ALLREDUCE for small messages by one hop of LL8 packets
+        through the ranks' LL scratch (mscclppAmdPullReduceLLLaunch): the same operations, operand order
+        and bits, no handshake.  scales / scale_tensors: as for pull_reduce, with op = PREMUL_SUM only."""
+        dt = reduce_code(inputs[0].dtype, accum)
+        nbytes = inputs[0].numel() * inputs[0].element_size() // (self.n if coll == PULL_REDUCE_SCATTER else 1)
+        arr = self.views(inputs, outputs)
+        imm = ptrs = None
+        if scales is not None or scale_tensors is not None:
+            imm = (ctypes.c_float * self.n)(*(scales if scales is not None else [0.0] * self.n))
+            if scale_tensors is not None:
+                ptrs = (ctypes.c_void_p * self.n)(*[None if t is None else t.data_ptr() for t in scale_tensors])
+        code = lib().mscclppAmdPullReduceLLLaunch(arr, self.n, self.n, coll, nbytes, dt, op, nblocks, nthreads,
+                                                  budget_ticks, stream_ptr(stream), imm, ptrs)
+        check(code, "in-process pull_reduce_ll")
 
     def send_recv(self, ops, nblocks=0, nthreads=0, budget_ticks=500_000_000, stream=None):
         """ncclSend / ncclRecv (a whole group) for in-process ranks, one launch.  ops: (src, dst, send,
@@ -814,6 +850,13 @@ class Communicator:
         check(lib().mscclppAmdCommRegistrationExchanges(self.comm, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
               "registration exchanges")
         return a.value, b.value, bool(c.value)
+
+    def pull_ll_count(self):
+        """Collective calls of this communicator that took the small-message LL path of the MAX / AVG /
+        int64 / uint64 / int8 / PreMulSum reductions (mscclppAmdCommPullLLCount)."""
+        c = ctypes.c_uint64()
+        check(lib().mscclppAmdCommPullLLCount(self.comm, ctypes.byref(c)), "pull LL count")
+        return c.value
 
     def destroy(self):
         if self.comm:

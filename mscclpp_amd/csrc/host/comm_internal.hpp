@@ -42,6 +42,11 @@ int launchPullReduce(const mscclppAmdRankView* views, int nviews, int nranks, in
                      int root, int nblocks, int nthreads, uint64_t budget, hipStream_t s, const float* scales = nullptr,
                      const void* const* scalePtrs = nullptr);
 int pullReduceDefaultBlocks(int coll, uint64_t bytes);
+int launchPullReduceLL(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes, int dtype, int op,
+                       int nblocks, int nthreads, uint64_t budget, hipStream_t s, const float* scales,
+                       const void* const* scalePtrs);
+size_t pullReduceLLScratchRequired(int coll, int nranks, size_t bytes, int dtype, int op);
+bool pullReduceTakesLL(int coll, int nranks, size_t bytes);
 int launchSendRecv(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdSendRecvOp* ops, int nops,
                    int nblocks, int nthreads, uint64_t budget, hipStream_t s);
 int sendrecvDefaultBlocks(uint64_t bytes);
@@ -798,6 +803,28 @@ struct ncclComm {
   int pullReduce(int coll, const void* send, void* recv, size_t bytes, int dtype, int op, int root, hipStream_t stream,
                  float scale = 0.0f, const void* scalePtr = nullptr) {
     std::lock_guard<std::mutex> lk(mu);
+    // Small AllReduce / ReduceScatter: one hop of LL8 packets through the LL scratch (kernels/
+    // pull_reduce_ll.hip) -- nothing is registered and no token is exchanged.  The
+    // rule is a function of (coll, nranks, bytes) and the environment, so every rank decides alike.
+    // Under capture a scratch that would have to grow cannot (ensure); such a call takes the pull
+    // path instead -- the capture state and llBytes are the same on every rank.
+    if (coll != MSCCLPP_AMD_PULL_REDUCE && pullReduceTakesLL(coll, nranks, bytes)) {
+      const size_t need = pullReduceLLScratchRequired(coll, nranks, bytes, dtype, op);
+      if (need && (need <= llBytes || !capturing(stream))) {
+        touched.clear();
+        mscclppAmdRankView v = baseView(send, recv);
+        ensure(llScratch, llBytes, peerLL, need, stream);
+        v.scratch = llScratch;
+        v.scratchBytes = llBytes;
+        for (int r = 0; r < nranks; ++r) v.peerScratch[r] = peerLL[r];
+        const bool scaled = op == MSCCLPP_AMD_PREMUL_SUM;
+        const int rc = launchPullReduceLL(&v, 1, nranks, coll, bytes, dtype, op, 0, 0, spinBudgetTicks(), stream,
+                                          scaled ? &scale : nullptr, scaled ? &scalePtr : nullptr);
+        recordUses(stream);
+        if (rc == 0) ++pullLLCount;
+        return rc;
+      }
+    }
     mscclppAmdRankView v = pullView(send, recv, stream);
     if (coll == MSCCLPP_AMD_PULL_ALLREDUCE) {
       if (recv == send) {  // in place: the same registration
@@ -812,6 +839,7 @@ struct ncclComm {
     recordUses(stream);
     return rc;
   }
+  uint64_t pullLLCount = 0;  // collective calls that took the LL path above (under mu)
 
   // ---- PreMulSum handles (ncclRedOpCreatePreMulSum / ncclRedOpDestroy) -----------
   // A handle's value is ncclNumOps + its slot; a destroyed slot is taken again by the next create.

@@ -760,4 +760,44 @@ int mscclppAmdPullReduceLaunchScaled(const mscclppAmdRankView* views, int nviews
 
 int mscclppAmdPullReduceDefaultBlocks(int coll, uint64_t bytes) { return mscclpp_amd::pullReduceDefaultBlocks(coll, bytes); }
 
+// The same reductions of a small AllReduce / ReduceScatter by one hop of LL8 packets, for in-process
+// ranks (and the one-view form the NCCL entry points launch): everything is checked before a device is
+// touched; a refusal launches nothing.  (The collective, the (dtype, op) pairs, the byte count and the
+// scalars: launchPullReduceLL, which answers 4 before it looks at a view.)
+int mscclppAmdPullReduceLLLaunch(const mscclppAmdRankView* views, int nviews, int nranks, int coll, size_t bytes,
+                                 int dtype, int op, int nblocks, int nthreads, uint64_t budgetTicks, void* stream,
+                                 const float* scales, const void* const* scalePtrs) {
+  return guarded([&] {
+    if (coll != MSCCLPP_AMD_PULL_REDUCE_SCATTER && coll != MSCCLPP_AMD_PULL_ALLREDUCE) return (int)ncclInvalidArgument;
+    ViewNeeds needs;
+    needs.all = kViewInput | kViewOutput | kViewScratch | kViewFlags | kViewErr | kViewPeerScratch;
+    if (!viewsValid(views, nviews, nranks, needs)) return (int)ncclInvalidArgument;
+    unsigned seen = 0;
+    for (int i = 0; i < nviews; ++i) {
+      const mscclppAmdRankView& v = views[i];
+      if ((seen >> v.rank) & 1u) return (int)ncclInvalidArgument;  // no rank twice
+      seen |= 1u << v.rank;
+      if ((uintptr_t)v.flags % 16) return (int)ncclInvalidArgument;  // 16-byte flag refresh
+    }
+    return mscclpp_amd::launchPullReduceLL(views, nviews, nranks, coll, bytes, dtype, op, nblocks, nthreads,
+                                           budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream, scales,
+                                           scalePtrs);
+  });
+}
+
+size_t mscclppAmdPullReduceLLScratchRequired(int coll, int nranks, size_t bytes, int dtype, int op) {
+  return mscclpp_amd::pullReduceLLScratchRequired(coll, nranks, bytes, dtype, op);
+}
+
+int mscclppAmdPullReduceTakesLL(int coll, int nranks, size_t bytes) {
+  return mscclpp_amd::pullReduceTakesLL(coll, nranks, bytes) ? 1 : 0;
+}
+
+int mscclppAmdCommPullLLCount(ncclComm_t comm, uint64_t* count) {
+  if (!comm || !count) return ncclInvalidArgument;
+  std::lock_guard<std::mutex> lk(comm->mu);
+  *count = comm->pullLLCount;
+  return ncclSuccess;
+}
+
 }  // extern "C"

@@ -21,6 +21,7 @@
 // pointers come from kernel arguments (scalar loads), not from channel handles copied to LDS; loops
 // over peers are unrolled to the 8-GPU maximum with predicates so the per-peer values stay in VGPRs.
 #include "launch.hpp"
+#include "ll_units.hpp"
 
 namespace mscclpp_amd {
 
@@ -47,53 +48,6 @@ struct LL8Geom {
   uint64_t hbEven;  // packets when the flag is odd / even (allreduce_test.cu:861-863)
 };
 
-// ---- packet-major units ------------------------------------------------------------------------
-// One lane owns one "unit": 8 payload bytes <-> 16 packet bytes, i.e. one LL16 packet
-// {P[2i], f, P[2i+1], f} or the two LL8 packets {P[2i], f}, {P[2i+1], f} -- the same 16-byte image.
-// Consecutive lanes own consecutive units, so every packet store / poll of a wave is one contiguous
-// 1 KiB access made of whole 64-byte lines (partial-line packet stores cost a full line each on
-// gfx950: WRITE_SIZE 5*S instead of 3*S in the self-reduce microbench), and the payload side is a
-// contiguous 512 B dwordx2 access.
-template <int Policy>
-__device__ __forceinline__ void unit_put(__amdgpu_buffer_rsrc_t pk, uint32_t pbyte, u32x2 w, uint32_t flag,
-                                         bool single) {
-  if (!single)
-    store16<Policy>(pk, pbyte, u32x4{w.x, flag, w.y, flag});
-  else
-    store8<Policy>(pk, pbyte, u32x2{w.x, flag});  // lone trailing LL8 packet
-}
-__device__ __forceinline__ bool unit_try(__amdgpu_buffer_rsrc_t pk, uint32_t pbyte, uint32_t flag, u32x2& w,
-                                         bool single) {
-  if (!single) {
-    u32x4 a = load16<kSystem>(pk, pbyte);
-    w = u32x2{a.x, a.z};
-    return a.y == flag && a.w == flag;
-  }
-  u32x2 a = load8<kSystem>(pk, pbyte);
-  w = u32x2{a.x, 0};
-  return a.y == flag;
-}
-// Timeout detail of one packet unit: the first of its flag words that differs from `flag`, re-read.
-__device__ __forceinline__ uint32_t unit_flag_seen(__amdgpu_buffer_rsrc_t pk, uint32_t pbyte, uint32_t flag,
-                                                   bool single) {
-  if (single) return load8<kSystem>(pk, pbyte).y;
-  const u32x4 a = load16<kSystem>(pk, pbyte);
-  return a.y != flag ? a.y : a.w;
-}
-__device__ __forceinline__ u32x2 unit_get(__amdgpu_buffer_rsrc_t pk, uint32_t pbyte, uint32_t flag, bool single,
-                                          uint64_t budget, uint32_t* err) {
-  u32x2 w;
-  if (unit_try(pk, pbyte, flag, w, single)) return w;
-  SpinGuard g(budget);
-  while (!unit_try(pk, pbyte, flag, w, single)) {
-    __builtin_amdgcn_s_sleep(1);
-    if (g.expired()) {
-      report_packet_timeout(err, flag, pbyte, unit_flag_seen(pk, pbyte, flag, single));
-      return u32x2{0, 0};
-    }
-  }
-  return w;
-}
 // add_vectors<TYPE>(a, b) of python/mscclpp_benchmark/allreduce.cu:37-96 on one 8-byte payload: int
 // wrapping adds, float `a + b`, __half __hadd2 -- round to nearest even and no clip (inf on overflow),
 // unlike the collectives' f16x2 operator+ (gpu_data_types.hpp:389-397).
@@ -118,24 +72,8 @@ __device__ __forceinline__ u32x2 bench_add2(u32x2 a, u32x2 b) {
   }
 }
 
-// First poll of unit `pbyte` in every peer's region (peer p's at p * stride of `base`): all loads
-// are issued, unconditionally and in one basic block, before any value is compared, so they are in
-// flight together (a compare right after each load, or a load under a branch, made the compiler wait
-// for it before issuing the next: one memory round trip per peer).  A slot that is not a peer (own
-// rank, p >= nranks) is loaded through a zero-length buffer resource: out of range, it returns zeros
-// without touching memory.  Returns the mask of peers whose packet had not landed; w[p] holds the
-// payload of the others.
-__device__ __forceinline__ void poll_issue(const uint8_t* base, uint32_t stride, uint32_t pbyte, uint32_t peers,
-                                           u32x4* raw) {
-#pragma unroll
-  for (int p = 0; p < kMaxRanks; ++p) {
-    const auto r = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(base), 0,
-                                                     ((peers >> p) & 1u) ? 0xFFFFFFFFu : 0u, 0x00020000);
-    raw[p] = load16<kSystem>(r, (uint32_t)p * stride + pbyte);
-  }
-}
-// As poll_issue, for a scratch whose source regions are indexed by peer, not by rank: source p sits
-// in slot p < rank ? p : p - 1 (mscclpp-test allreduce2, allreduce_test.cu:876-880).
+// As poll_issue (ll_units.hpp), for a scratch whose source regions are indexed by peer, not by rank:
+// source p sits in slot p < rank ? p : p - 1 (mscclpp-test allreduce2, allreduce_test.cu:876-880).
 __device__ __forceinline__ void poll_issue_peer_slots(const uint8_t* base, uint32_t stride, uint32_t pbyte,
                                                       uint32_t peers, int rank, u32x4* raw) {
 #pragma unroll
@@ -145,21 +83,6 @@ __device__ __forceinline__ void poll_issue_peer_slots(const uint8_t* base, uint3
     raw[p] = load16<kSystem>(r, (uint32_t)(p < rank ? p : p - 1) * stride + pbyte);
   }
 }
-__device__ __forceinline__ uint32_t poll_eval(const u32x4* raw, uint32_t flag, uint32_t peers, u32x2* w) {
-  uint32_t missing = 0;
-#pragma unroll
-  for (int p = 0; p < kMaxRanks; ++p) {
-    w[p] = u32x2{raw[p].x, raw[p].z};
-    if (raw[p].y != flag || raw[p].w != flag) missing |= 1u << p;
-  }
-  return missing & peers;
-}
-__device__ __forceinline__ uint32_t poll_units(const uint8_t* base, uint32_t stride, uint32_t pbyte, uint32_t flag,
-                                               uint32_t peers, u32x2* w) {
-  u32x4 raw[kMaxRanks];
-  poll_issue(base, stride, pbyte, peers, raw);
-  return poll_eval(raw, flag, peers, w);
-}
 // Diagnostics build only (variant bit 32): add n, summed over the wave, to *ctr (first-poll misses).
 template <int V>
 __device__ __forceinline__ void count_misses(uint32_t* ctr, uint32_t n) {
@@ -167,19 +90,6 @@ __device__ __forceinline__ void count_misses(uint32_t* ctr, uint32_t n) {
     for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
     if ((threadIdx.x & 63) == 0 && n) __hip_atomic_fetch_add(ctr, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-}
-// A unit whose first poll missed: spin until it lands (the caller keeps the values of the units
-// that were ready, so only the missing ones are read again).
-__device__ __forceinline__ u32x2 unit_wait(__amdgpu_buffer_rsrc_t pk, uint32_t pbyte, uint32_t flag, bool single,
-                                           uint64_t budget, uint32_t* err) {
-  u32x2 w;
-  SpinGuard g(budget);
-  do {
-    __builtin_amdgcn_s_sleep(1);
-    if (unit_try(pk, pbyte, flag, w, single)) return w;
-  } while (!g.expired());
-  report_packet_timeout(err, flag, pbyte, unit_flag_seen(pk, pbyte, flag, single));
-  return u32x2{0, 0};
 }
 // Wave-level readiness probe (LL16 step 3 from kSentinelUnits units per slice): one lane polls the
 // last unit the wave covers in this pass (one line) until it has landed, so the wave's full poll that
@@ -206,29 +116,6 @@ __device__ __forceinline__ void sentinel_wait(__amdgpu_buffer_rsrc_t pk, uint32_
     if (probe()) return;
   } while (!g.expired());
 }
-// 8-byte payload at byte `off` of `base`, of which `valid` bytes are inside the buffer
-__device__ __forceinline__ u32x2 payload_ld(__amdgpu_buffer_rsrc_t r, const uint8_t* base, uint64_t off, uint32_t valid) {
-  if (valid >= 8) return load8<kPlain>(r, (uint32_t)off);
-  uint32_t w0 = 0, w1 = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    if ((uint32_t)i < valid) {
-      const uint32_t v = (uint32_t)base[off + i] << ((i % 4) * 8);
-      if (i < 4) w0 |= v; else w1 |= v;
-    }
-  }
-  return u32x2{w0, w1};
-}
-__device__ __forceinline__ void payload_st(__amdgpu_buffer_rsrc_t r, uint8_t* base, uint64_t off, u32x2 v, uint32_t valid) {
-  if (valid >= 8) {
-    store8<kPlain>(r, (uint32_t)off, v);
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-    if ((uint32_t)i < valid) base[off + i] = (uint8_t)((i < 4 ? v.x : v.y) >> ((i % 4) * 8));
-}
-
 // V (0 in the product): bits that switch a part back to its round-2 form, for same-process A/B
 // timing through the diagnostics build (MSCCLPP_AMD_DIAG): 4 = polls tested as issued and every peer
 // re-read after a miss, 8 = a scalar flag load ahead of everything else, 16 = every slice size polls
@@ -500,18 +387,6 @@ __global__ void __launch_bounds__(512) allreduceLL8Kernel(Views<NV> views, LL8Ge
 }
 
 // ---- host-side geometry + launch -------------------------------------------------------------------
-// 32-bit words the LL kernels cover: (count*sizeof(T)+sizeof(T))/sizeof(int) for 1- and 2-byte T
-// (allreduce_packet.cu:51-52, allreduce_allpair_packet.cu:20).  Deviation: for 1-byte T with
-// count % 4 in {1, 2} that stops short of the buffer (its last bytes would never be reduced), so
-// the words are rounded up there; every other size keeps the reference's count.
-static inline uint64_t llWords(size_t bytes, int dtype) {
-  const int es = elem_bytes(dtype);
-  if (es == 4) return bytes / 4;
-  uint64_t W = (bytes + es) / 4;
-  if (W * 4 < bytes) W = (bytes + 3) / 4;
-  return W;
-}
-
 static LL16Geom ll16Geometry(int nranks, size_t bytes, int dtype) {
   LL16Geom g{};
   g.trace = g_mscclppAmdTrace;
@@ -582,14 +457,6 @@ static bool testK2Geometry(int nranks, size_t bytes, LL8Geom* out) {
   return true;
 }
 
-// The LL kernels address a buffer, and all source regions of a scratch half, from one buffer
-// resource each (32-bit offsets: the whole packet exchange of a bucket stays in one descriptor, no
-// per-unit rebasing on the latency path).  So an LL bucket is bounded: its bytes, and the n regions
-// of a scratch half, must lie within 4 GiB of their base -- LL16 to just under 2 GiB per rank,
-// LL8 to 2 GiB / n; beyond, the call is refused (ncclInvalidUsage) rather than wrapped.  The
-// reference runs these protocols below 1 MiB (algorithm_selector.cc:107-117); larger buckets take the
-// bulk paths, which rebase per workgroup and per pass.
-constexpr uint64_t kLLOffsetLimit = 0xFFFFFFFFull - 64;
 static bool ll16Fits(int nranks, const LL16Geom& g) {
   return g.bytes <= kLLOffsetLimit && (uint64_t)nranks * g.ppr * 16 <= kLLOffsetLimit;
 }

@@ -24,6 +24,12 @@ profiles/int_reduce_perf_inprocess_n8.json.
 
 TYPES=premul: PreMulSum beside AVG of the same type and collective, fp16 / bf16 / fp32,
 SIZES 64 KiB, 1 MiB and 48 MiB by default; the result goes to profiles/premul_sum_perf_inprocess_n8.json.
+
+TYPES=ll: the small-message LL path (kernels/pull_reduce_ll.hip) beside the pull launcher
+at its default grid and the LL8 SUM AllReduce, alternating in the same run: AllReduce and ReduceScatter
+of fp32 MAX, fp16 AVG and int64 SUM, 4 bytes .. 1 MiB in powers of two (the message, or a ReduceScatter's
+per-rank block), NRANKS ranks.  The result, with the cutover read off it, goes to
+profiles/pull_reduce_ll_perf_inprocess_n{NRANKS}.json.
 """
 import json
 import os
@@ -211,6 +217,112 @@ def premul_programme():
     json.dump(res, open(out, "w"), indent=1)
 
 
+def ll_programme():
+    """LL path against the pull launcher (default grids) and the LL8 SUM AllReduce.  S: the message of an
+    AllReduce, the per-rank block of a ReduceScatter -- what the cutover rule is a function of."""
+    sizes = [int(s) for s in os.environ.get("SIZES", ",".join(str(1 << k) for k in range(2, 21))).split(",")]
+    kinds = (("f32_max", torch.float32, 4, m.MAX), ("f16_avg", torch.float16, 2, m.AVG), ("i64_sum", torch.int64, 8, m.SUM))
+    colls = (("allreduce", m.PULL_ALLREDUCE), ("reducescatter", m.PULL_REDUCE_SCATTER))
+    need = max(m.pull_reduce_ll_scratch_required(c, N, max(sizes), m.F32, m.MAX) for _, c in colls)
+    need = max(need, m.scratch_required(m.ALGO_ALLPAIR, N, max(sizes), m.F32), 1 << 16)
+    ranks = m.InProcessRanks(N, need)
+    rows = []
+    for S in sizes:
+        for cname, coll in colls:
+            mult = N if coll == m.PULL_REDUCE_SCATTER else 1
+            bufs = {}
+            for name, tdt, es, op in kinds:
+                if S % es:
+                    continue
+                count = S // es
+                if tdt == torch.int64:
+                    x = [torch.randint(-2 ** 40, 2 ** 40, (count * mult,), dtype=tdt, device=dev) for _ in range(N)]
+                else:
+                    x = [torch.rand(count * mult, dtype=torch.float32, device=dev).to(tdt) for _ in range(N)]
+                bufs[name] = (x, [torch.zeros(count, dtype=tdt, device=dev) for _ in range(N)],
+                              [torch.zeros(count, dtype=tdt, device=dev) for _ in range(N)], op)
+
+            def ll(name):
+                x, y, _, op = bufs[name]
+                ranks.pull_reduce_ll(coll, x, y, op, budget_ticks=BUDGET, stream=cur())
+
+            def pull(name):
+                x, _, z, op = bufs[name]
+                ranks.pull_reduce(coll, x, z, op, budget_ticks=BUDGET, stream=cur())
+
+            def ll8_sum():
+                x, y, _, _ = bufs["f32_max"]
+                ranks.all_reduce(x, y, m.ALGO_ALLPAIR, budget_ticks=BUDGET, stream=cur())
+
+            ll8_runs = coll == m.PULL_ALLREDUCE
+            if ll8_runs:  # (its default grid of 512-lane workgroups is not resident for 4 and 8 ranks on one GPU from 512 KiB)
+                try:
+                    ll8_sum()
+                except m.MscclppError as e:
+                    assert e.code == 5
+                    ll8_runs = False
+
+            ok = True
+            for name in bufs:  # what is timed gives the same bytes on both paths
+                ll(name)
+                pull(name)
+                torch.cuda.synchronize()
+                ok = ok and all(torch.equal(a, b) for a, b in zip(bufs[name][1], bufs[name][2]))
+            ok = ok and ranks.errors() == [0] * N
+            lines = []
+            for name in bufs:
+                lines += [("ll_" + name, (lambda k=name: ll(k))), ("pull_" + name, (lambda k=name: pull(k)))]
+            if ll8_runs:
+                lines.append(("sum_allreduce_ll8_f32", ll8_sum))
+            calls, replays = (20, 5) if S >= (256 << 10) else (50, 10)
+            t = {name: [] for name, _ in lines}
+            for _ in range(ROUNDS):
+                for name, fn in lines:
+                    t[name].append(graph_us(fn, calls, replays))
+            row = {"coll": cname, "bytes": S, "correct": bool(ok), "graph_calls": calls, "replays": replays, "rounds": ROUNDS,
+                   "lines": {name: stat(v) for name, v in t.items()}}
+            row["ll_beats_pull"] = {name: row["lines"]["ll_" + name]["us"] < row["lines"]["pull_" + name]["us"] for name in bufs}
+            if coll == m.PULL_ALLREDUCE and S <= 1024:
+                base = row["lines"]["sum_allreduce_ll8_f32"]
+                row["ll_f32_max_over_ll8_sum"] = round(row["lines"]["ll_f32_max"]["us"] / base["us"], 3)
+                row["ll8_sum_spread_us"] = round(base["us_min_max"][1] - base["us_min_max"][0], 2)
+                if S == 1024:
+                    phases = {}
+                    for label, fn, fam in (("ll_f32_max", lambda: ll("f32_max"), "pull_reduce_ll"), ("ll8_sum", ll8_sum, "allpair")):
+                        with m.PhaseTrace() as tr:
+                            fn()
+                            torch.cuda.synchronize()
+                        phases[label] = tr.phases(fam, view=0)
+                    row["phases"] = phases
+            row["errors"] = ranks.errors()
+            rows.append(row)
+            print(row, flush=True)
+            del bufs
+    # the rule: per collective the largest swept size such that at it and at every smaller swept size the LL
+    # median beats the pull median for all three (dtype, op)
+    cutover = {}
+    for cname, _ in colls:
+        best = 0
+        for row in sorted((r for r in rows if r["coll"] == cname), key=lambda r: r["bytes"]):
+            if not all(row["ll_beats_pull"].values()):
+                break
+            best = row["bytes"]
+        cutover[cname] = best
+    res = {"tool": "tools/pull_reduce_perf.py TYPES=ll", "fabric_free": True, "gpus": 1, "nranks": N,
+           "note": "in-process ranks on one GPU: no xGMI byte is priced (the LL path writes 2 (n - 1) x the message "
+                   "over the links, the pull path reads 2 (n - 1) / n x); graph-captured, median of rounds; bytes = the "
+                   "message of an AllReduce, the per-rank block of a ReduceScatter",
+           "cutover_bytes": cutover, "rows": rows}
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = os.environ.get("OUT", os.path.join(root, "profiles", f"pull_reduce_ll_perf_inprocess_n{N}.json"))
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    json.dump(res, open(out, "w"), indent=1)
+    print("cutover", cutover, flush=True)
+
+
+if os.environ.get("TYPES") == "ll":
+    ll_programme()
+    sys.exit(0)
 if os.environ.get("TYPES") == "int64":
     int64_programme()
     sys.exit(0)
