@@ -589,9 +589,12 @@ struct ncclComm {
 
   // Peer pointers of a user buffer (the bulk kernels write results straight into every peer's
   // output, allreduce_fullmesh.cu:110-113; zero-copy reads the peers' inputs).  Cached per local
-  // allocation like the reference's per-buffer context cache (algorithm.cc:52-60): a repeated call on
-  // the same buffer costs no host round trip.  As in the reference, every rank must pass its
-  // matching buffer when a buffer is first used.
+  // pointer, inside a record per local allocation, like the reference's per-buffer context cache
+  // (algorithm.cc:52-60): a repeated call on the same buffer costs no host round trip.  As in the
+  // reference, every rank must pass its matching buffer when a buffer is first used; which of a
+  // rank's buffers share an allocation is free to differ between ranks (each new pointer brings
+  // every rank's own allocation and offset).  Eviction is by local allocation, so beyond
+  // kMaxUserRegs allocations the ranks must still group alike to evict alike.
   //  * The allocation is identified by (base, size, HIP buffer id): a buffer freed and re-allocated
   //    at the same address is a new allocation, registered afresh, and its old registration retired.
   //  * At most kMaxUserRegs allocations stay registered; the least recently used one is retired
@@ -620,7 +623,10 @@ struct ncclComm {
     uint64_t bufferId = 0;
     uint64_t lastUse = 0;
     bool pinned = false;  // used under stream capture
-    PeerBufs bases;
+    PeerBufs bases;  // symmetric memory only: every rank's allocation, exchanged once
+    // every peer mapping a pointer of this allocation was resolved through (registerOutput, one per
+    // peer allocation): open for as long as the registration lives
+    std::vector<std::shared_ptr<void>> held;
     UseEvents uses;
     std::map<uint64_t, std::array<void*, MSCCLPP_AMD_MAX_RANKS>> byOffset;
     // (allocation base, HIP buffer id) of every rank's buffer this one was exchanged with (pairedRegs)
@@ -640,6 +646,8 @@ struct ncclComm {
            std::to_string(it->first.first) + " retired (its address now belongs to a new allocation)");
     Retired r;
     for (auto& m : it->second.bases.maps)
+      if (m) r.maps.push_back(std::move(m));
+    for (auto& m : it->second.held)
       if (m) r.maps.push_back(std::move(m));
     r.uses = std::move(it->second.uses);
     for (auto t = touched.begin(); t != touched.end();)  // not recorded for a launch any more
@@ -674,7 +682,9 @@ struct ncclComm {
       evictFor(userRegs);
       UserReg reg;
       reg.bufferId = bid;
-      reg.bases = exchange(base);  // collective: every rank registers its matching buffer now
+      // symmetric memory: every rank's matching allocation, exchanged now (collective); otherwise the
+      // peers' allocations come with each new pointer below
+      if (symmetricMemory) reg.bases = exchange(base);
       ++allocExchanges;
       it = userRegs.emplace(key, std::move(reg)).first;
     }
@@ -688,16 +698,28 @@ struct ncclComm {
     const uint64_t off = (uint64_t)((char*)out - (char*)base);
     auto pit = reg.byOffset.find(off);
     if (pit == reg.byOffset.end()) {
-      // The offset of `out` inside its allocation may differ between ranks: exchange offsets (cheap)
-      // to build exact pointers -- unless the application declared symmetric allocation, where it
-      // is the same on every rank and this call stays local.
-      std::vector<uint64_t> offs(nranks, off);
-      if (!symmetricMemory) {
-        boot->allGather(&off, offs.data(), sizeof(off));
-        ++offsetExchanges;
-      }
       std::array<void*, MSCCLPP_AMD_MAX_RANKS> res{};
-      for (int r = 0; r < nranks; ++r) res[r] = (r == rank) ? out : (char*)reg.bases[r] + offs[r];
+      if (symmetricMemory) {
+        // the application declared symmetric allocation: the offset is the same on every rank and
+        // this call stays local
+        for (int r = 0; r < nranks; ++r) res[r] = (r == rank) ? out : (char*)reg.bases[r] + off;
+      } else {
+        // A pointer this rank has not passed before: one host all-gather carries every rank's
+        // allocation (handle, base, bytes) and the offset of ITS buffer inside it, and each peer
+        // pointer is built from that rank's own pair.  Which of a rank's buffers share an allocation
+        // is its allocator's business -- a caching allocator fed rank-dependent sizes groups them
+        // differently per rank -- so no peer base cached for the local allocation may be combined with
+        // an offset the peer took in another one (that read foreign memory, with no error).  The call
+        // is collective exactly when the buffer is new, which every rank sees alike (every rank passes
+        // its matching buffer); a peer allocation already mapped is found open (openIpcHandle).
+        PeerBufs now = exchange(out);
+        ++offsetExchanges;
+        for (int r = 0; r < nranks; ++r) {
+          res[r] = now[r];
+          auto& m = now.maps[(size_t)r];
+          if (m && std::find(reg.held.begin(), reg.held.end(), m) == reg.held.end()) reg.held.push_back(std::move(m));
+        }
+      }
       pit = reg.byOffset.emplace(off, res).first;
     }
     const auto res = pit->second;

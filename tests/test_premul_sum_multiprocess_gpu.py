@@ -1,10 +1,19 @@
-"""ncclRedOpCreatePreMulSum / ncclRedOpDestroy and the collectives that take their handles, through the
-NCCL ABI, one rank per process (placed by mp_util), no vendor library.  The sequence is PyTorch's
-(ProcessGroupNCCL): create the operation with a host-immediate scalar of the element type, call the
-collective, destroy the operation at once -- before the stream has run -- and only then synchronise.
-Results are compared bit for bit with the numpy reference of premul_sum_cases (any NaN where it is
-NaN), which every rank computes from all ranks' inputs and scalars; every worker runs under the
-collect() watchdog from its first call."""
+"""ncclRedOpCreatePreMulSum / ncclRedOpDestroy and the collectives that take their handles, through the NCCL
+ABI, one rank per process (placed by mp_util), no vendor library, on both kernels the dispatch chooses
+between.  Every row is in abi_path_cases.PREMUL with the path it means to take, and every ncclAllReduce /
+ncclReduceScatter / ncclReduce call is checked against the communicator's own account
+(abi_path_cases.Account).  Each rank count runs twice: "pull" (MSCCLPP_AMD_PULL_LL_MAX_BYTES=0) sends
+every call to the pull-reduce kernel (kernels/pull_reduce.hip), where the scalars travel through the
+token diagonal (written, read by the peers, zeroed again) -- host immediates, the device-resident scalar,
+create / call / destroy at once and the graph replay with changed scalars; "ll" (the default environment)
+sends the same AllReduce and ReduceScatter rows to the LL kernel (kernels/pull_reduce_ll.hip), where the
+scalar rides in the packets, and then runs a bf16 AllReduce with a device-resident scalar and an fp32
+ReduceScatter in place at exactly the built-in cutover (LL) and one element above it (pull, on fresh
+buffers).  The sequence is PyTorch's (ProcessGroupNCCL): create the operation with a host-immediate scalar
+of the element type, call the collective, destroy the operation at once -- before the stream has run --
+and only then synchronise. Results are compared bit for bit with the numpy reference of premul_sum_cases
+(any NaN where it is NaN), which every rank computes from all ranks' inputs and scalars; every worker
+runs under the collect() watchdog from its first call."""
 import multiprocessing as mp
 import os
 import traceback
@@ -34,10 +43,13 @@ def _spawn(target, n, timeout=240, *extra):
     return mp_util.collect(procs, q, n, timeout)
 
 
-def _setup(rank, n, uid):
+def _setup(rank, n, uid, mode):
     os.environ.setdefault("MSCCLPP_AMD_SPIN_TIMEOUT_MS", "10000")
     os.environ.pop("MSCCLPP_AMD_NCCL_LIB_PATH", None)  # no vendor library
     os.environ.pop("MSCCLPP_NCCL_LIB_PATH", None)
+    import abi_path_cases as T
+
+    T.set_mode(mode)  # before the library is imported: it reads the variable once
     import torch
 
     import mscclpp_amd as m
@@ -46,17 +58,19 @@ def _setup(rank, n, uid):
     return torch, m, m.Communicator(rank, n, uid), dev, shared
 
 
-def _worker(rank, n, uid, q):
+def _worker(rank, n, uid, q, mode):
     try:
-        torch, m, comm, dev, shared = _setup(rank, n, uid)
+        torch, m, comm, dev, shared = _setup(rank, n, uid, mode)
         import ctypes
 
         import numpy as np
 
+        import abi_path_cases as T
         import oracle_lib as O
         import premul_sum_cases as C
 
         res = {"device": dev, "shared": shared}
+        acct = T.Account(comm, n, mode)
         nccl_type = {O.F16: NCCL_FLOAT16, O.BF16: NCCL_BFLOAT16, O.F32: NCCL_FLOAT32}
         tdt = {O.F16: torch.float16, O.BF16: torch.bfloat16, O.F32: torch.float32}
         L = m.lib()
@@ -118,8 +132,10 @@ def _worker(rank, n, uid, q):
             ok = ok and C.mismatches(code, got[24:24 + cnt * es].view(C.bits_dtype(code)), ref[mine]).size == 0
             return ok and bool((got[:24] == FILL).all()) and bool((got[24 + cnt * es:] == FILL).all())
 
-        def run(coll, code, cnt, ss, inplace=False, root=0):
-            """PyTorch's sequence with new data; True when this rank's result, guards and send buffer are right."""
+        def run(row, ss, root=0):
+            """PyTorch's sequence of a table row with new data, under the account; True when this rank's
+            result, guards and send buffer are right."""
+            coll, code, cnt, inplace = row.coll, row.code, T.count_of(row, n), row.inplace
             xs, ref, send, recv = load(coll, code, cnt, ss, inplace)
             receives = coll != C.REDUCE or rank == root
             keep = host_scalar(code, ss[rank])
@@ -127,25 +143,29 @@ def _worker(rank, n, uid, q):
             if rc != 0 or h < NCCL_NUM_OPS:
                 return False
             rp = recv.data_ptr() if receives or (not inplace and seed[0] % 2) else None
-            rc = call(coll, send.data_ptr(), rp, cnt, nccl_type[code], h, root)
+            rc = acct.call(row, lambda: call(coll, send.data_ptr(), rp, cnt, nccl_type[code], h, root), send.data_ptr(),
+                           recv.data_ptr())
             gone = L.ncclRedOpDestroy(h, comm.comm)  # at once: the stream has not run yet
             torch.cuda.synchronize()
             return rc == 0 and gone == 0 and judge(coll, code, cnt, xs, ref, inplace, root)
 
-        for code in (O.BF16, O.F32):
-            for k, coll in enumerate(C.COLLS):
-                name = "%s_coll%d" % (C.NAMES[code], coll)
-                res[name + "_fsdp"] = run(coll, code, count, C.fsdp_scalars(code, n), root=k % n)
-                res[name + "_per_rank"] = run(coll, code, count, C.scalars(code, n, seed[0], "special"), root=(k + 1) % n)
-                res[name + "_in_place"] = run(coll, code, count, C.scalars(code, n, seed[0], "generic"), inplace=True,
-                                              root=(k + 1) % n)
-        res["f16_once"] = run(C.REDUCE_SCATTER, O.F16, count, C.scalars(O.F16, n, 77, "generic"))
-        res["one_element"] = run(C.ALLREDUCE, O.F32, 1, C.scalars(O.F32, n, 78, "generic"))
+        for row in T.part(T.PREMUL, "main"):
+            code, k = row.code, C.COLLS.index(row.coll)
+            if row.key.endswith("_fsdp"):
+                res[row.key] = run(row, C.fsdp_scalars(code, n), root=k % n)
+            else:
+                kind = "generic" if row.inplace else "special"
+                res[row.key] = run(row, C.scalars(code, n, seed[0], kind), root=(k + 1) % n)
+        assert len(res) == 2 + 2 * 3 * 3
+        once, one = T.part(T.PREMUL, "once")
+        res[once.key] = run(once, C.scalars(O.F16, n, 77, "generic"))
+        res[one.key] = run(one, C.scalars(O.F32, n, 78, "generic"))
         # the Communicator methods: a Python factor (rounded to the dtype, a host immediate) and a handle as op=
         ss = C.fsdp_scalars(O.BF16, n)
         xs, ref, send, recv = load(C.REDUCE_SCATTER, O.BF16, count, ss, False)
         h = comm.create_premul_sum(1.0 / (2 * n), torch.bfloat16)
-        comm.reduce_scatter(send.view(torch.bfloat16), recv.view(torch.bfloat16), op=h)
+        acct.call(T.part(T.PREMUL, "communicator")[0],
+                  lambda: comm.reduce_scatter(send.view(torch.bfloat16), recv.view(torch.bfloat16), op=h), send.data_ptr())
         comm.destroy_op(h)
         torch.cuda.synchronize()
         res["communicator_methods"] = judge(C.REDUCE_SCATTER, O.BF16, count, xs, ref, False, 0)
@@ -156,15 +176,19 @@ def _worker(rank, n, uid, q):
         dev_scalar = torch.from_numpy(C.scalar_bits(code, [ss[rank]]).view(np.uint8).copy()).cuda()
         rc, hdev = create(dev_scalar.data_ptr(), nccl_type[code], DEVICE)
         xs, ref, send, recv = load(coll, code, count, ss, False)
-        ok = rc == 0 and call(coll, send.data_ptr(), recv.data_ptr(), count, nccl_type[code], hdev, 0) == 0
+        ok = rc == 0 and acct.call(T.part(T.PREMUL, "device")[0],
+                                   lambda: call(coll, send.data_ptr(), recv.data_ptr(), count, nccl_type[code], hdev, 0),
+                                   send.data_ptr(), recv.data_ptr()) == 0
         torch.cuda.synchronize()
         res["device_scalar"] = ok and judge(coll, code, count, xs, ref, False, 0)
         if n == 2:  # ... captured, and replayed after the scalar and the data were changed
             s = torch.cuda.Stream()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=s):
-                rc = L.ncclAllReduce(send.data_ptr(), recv.data_ptr(), count, nccl_type[code], hdev, comm.comm,
-                                     m.stream_ptr(torch.cuda.current_stream()))
+                rc = acct.call(T.part(T.PREMUL, "graph")[0],
+                               lambda: L.ncclAllReduce(send.data_ptr(), recv.data_ptr(), count, nccl_type[code], hdev, comm.comm,
+                                                       m.stream_ptr(torch.cuda.current_stream())),
+                               send.data_ptr(), recv.data_ptr())
             ok = rc == 0
             for it in range(2):
                 ss = C.scalars(code, n, 81 + it, C.KINDS[it])
@@ -213,6 +237,11 @@ def _worker(rank, n, uid, q):
         y = comm.all_reduce(x, torch.empty_like(x), op="sum")
         torch.cuda.synchronize()
         res["plain_all_reduce"] = bool((y == n * (n + 1) / 2).all())
+        # the default dispatch as a user meets it: at exactly the cutover (LL), one element above it (pull)
+        for row, case_seed in T.cutover_rows(T.PREMUL, mode):
+            res[row.key] = T.run_fresh(torch, comm, rank, acct, row, case_seed)
+        res["paths"] = acct.wrong
+        res["calls"] = dict(acct.calls)
         res["err"] = comm.device_error()
         comm.barrier()
         comm.destroy()
@@ -222,8 +251,9 @@ def _worker(rank, n, uid, q):
 
 
 @pytest.mark.parametrize("n", [2, 8])
-def test_premul_sum_through_the_nccl_abi(built, n):
-    got = _spawn(_worker, n)
+@pytest.mark.parametrize("path", ["ll", "pull"])
+def test_premul_sum_through_the_nccl_abi(built, path, n):
+    got = _spawn(_worker, n, 240, path)
     ndev = mp_util.export_device_count()
     devices = {got[r]["device"] for r in range(n)}
     assert len(devices) == min(n, max(1, ndev)), devices  # distinct GPUs where the machine has them
@@ -240,4 +270,10 @@ def test_premul_sum_through_the_nccl_abi(built, n):
         assert res.pop("create_bad_residence") == INVALID_ARGUMENT, (rank, got[rank])
         assert res.pop("create_null_scalar") == INVALID_ARGUMENT and res.pop("create_null_op") == INVALID_ARGUMENT
         assert (n == 2) == ("graph" in res)
+        # (part, key, coll, declared path, rise of pull_ll_count, exchanges before, after) of every call that
+        # did not take the path its row declares
+        assert res.pop("paths") == [], (rank, path)
+        calls = res.pop("calls")
+        assert calls["pull"] > 0 and (calls["ll"] > 0) == (path == "ll"), (rank, calls)
+        assert ("one_element_above_bf16_premulsum_coll2" in res) == ("one_element_above_f32_premulsum_coll1" in res) == (path == "ll")
         assert not [k for k, ok in res.items() if not ok], (rank, res)
