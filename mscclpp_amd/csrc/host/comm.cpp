@@ -638,13 +638,11 @@ int mscclppAmdCommRegistrationStats(ncclComm_t comm, size_t* userRegistrations, 
                                     size_t* retiredMappings) {
   if (!comm) return ncclInvalidArgument;
   std::lock_guard<std::mutex> lk(comm->mu);
-  if (userRegistrations) *userRegistrations = comm->userRegs.size() + comm->pairedRegs.size();
+  if (userRegistrations) *userRegistrations = comm->registrations();
   if (liveMappings) *liveMappings = liveIpcMappings();
   if (retiredMappings) {  // mappings still waiting for their last launches to complete
-    comm->flushRetired();
-    size_t k = 0;
-    for (const auto& r : comm->retired) k += r.maps.size();
-    *retiredMappings = k;
+    comm->mappings.flush(comm->device);
+    *retiredMappings = comm->mappings.pendingMaps();
   }
   return ncclSuccess;
 }

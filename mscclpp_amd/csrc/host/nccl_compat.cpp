@@ -178,11 +178,6 @@ static ncclResult_t unavailable(const char* what) {
   return ncclInternalError;
 }
 
-static bool rangesOverlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + nb && y < x + na;
-}
-
 // ---- Send / Recv and group calls -----------------------------------------------------------------
 // A byte move by the zero-copy pull kernel (kernels/sendrecv.hip, ncclComm::p2pPost / p2pMatch /
 // p2pLaunch).  A call outside a group is a group of one.  At the outermost ncclGroupEnd all sends
@@ -270,7 +265,7 @@ int p2pCall(bool send, const void* sendbuff, void* recvbuff, size_t count, ncclD
     if (peer == comm->rank) return (int)unavailable(what);
   }
   if (tb == 0 || (send ? !sendbuff : !recvbuff)) return (int)ncclInvalidArgument;
-  if (ncclComm::capturing((hipStream_t)stream)) {
+  if (streamCapturing((hipStream_t)stream)) {
     warn(std::string(what) + " exchanges a message between the hosts on every call, which a captured graph cannot replay");
     return (int)ncclInvalidUsage;
   }
@@ -379,7 +374,7 @@ ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, nccl
     const size_t bytes = count * ncclTypeBytes(datatype);
     // in place on the root is send == recv; any other overlap would have the root store into
     // bytes of its send buffer that another lane still reads
-    if (isRoot && bytes && sendbuff != recvbuff && rangesOverlap(sendbuff, bytes, recvbuff, bytes)) {
+    if (isRoot && bytes && sendbuff != recvbuff && bufferRangesOverlap(sendbuff, bytes, recvbuff, bytes)) {
       warn("ncclReduce: the root's send and receive ranges overlap without being identical");
       return (int)ncclInvalidArgument;
     }
@@ -433,7 +428,7 @@ ncclResult_t ncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, nc
     // and a pull would race with the peers' reads
     const size_t n = (size_t)comm->nranks, bytes = count * ncclTypeBytes(datatype);
     if (!sendbuff || !recvbuff || bytes == 0) return (int)ncclInvalidArgument;
-    if (rangesOverlap(sendbuff, n * bytes, recvbuff, n * bytes)) {
+    if (bufferRangesOverlap(sendbuff, n * bytes, recvbuff, n * bytes)) {
       warn("ncclAllToAll: the send and receive buffers overlap");
       return (int)ncclInvalidArgument;
     }
@@ -505,7 +500,7 @@ ncclResult_t ncclAllToAllv(const void* sendbuff, const size_t sendcounts[], cons
         }
       }
       if (sLo < sHi && rLo < rHi &&
-          rangesOverlap((const char*)sendbuff + sLo, sHi - sLo, (const char*)recvbuff + rLo, rHi - rLo)) {
+          bufferRangesOverlap((const char*)sendbuff + sLo, sHi - sLo, (const char*)recvbuff + rLo, rHi - rLo)) {
         warn("ncclAllToAllv: the send and receive ranges overlap");
         mine.ok = 0;
       }

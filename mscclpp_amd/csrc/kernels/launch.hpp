@@ -3,6 +3,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "launchers.hpp"  // what the host runtime calls: a kernel source defines what is declared there
 
 namespace mscclpp_amd {
 

@@ -4,7 +4,7 @@ Two rank processes cycle 70 distinct output allocations -- more than a registrat
 the least recently used registrations are retired while the calls go on -- through ncclAllReduce
 while a long kernel (torch.cuda._sleep, ~3 s) runs on another stream of the same device.  A retired
 mapping now closes when the events recorded after its last launches have completed
-(comm_internal.hpp flushRetired), and a freed pooled block waits in the pool's pending list instead
+(peer_mappings.cpp RetireQueue::flush), and a freed pooled block waits in the pool's pending list instead
 of synchronizing (uncached_pool.cpp): so the 70 calls and 8 frees of pooled blocks return while the
 other stream is still busy, and every one of the 70 results is bit-exact against the CPU oracle.
 Then the first 8 (evicted) outputs are used again while their old mappings are still queued for

@@ -261,6 +261,72 @@ def test_mixed_sequence_keeps_token_channels_in_step(built):
         assert got[rank] == [True, True, 0], (rank, got[rank])
 
 
+KEPT_CAP = 64  # ncclComm::kP2pKept: imports of one peer's send allocations a receiver keeps open
+
+
+def _kept_cap_worker(rank, n, uid, q):
+    try:
+        import time
+
+        torch, m, comm = _setup(rank, n, uid)
+        count, nbuf = 256, KEPT_CAP + 2
+        res = {"wrong": [], "closed": []}
+        if rank == 0:
+            # one hipMalloc per send buffer (torch's allocator would carve them from one segment,
+            # i.e. one import at the receiver)
+            bufs = [m.DeviceBuffer(count * 4, uncached=False) for _ in range(nbuf)]
+            sends = [m.device_view(b.ptr, count * 4).view(torch.float32) for b in bufs]
+            for i, s in enumerate(sends):
+                s.copy_(_pattern(torch, 0, count, torch.float32, i))
+        recv = _Guarded(torch, count, torch.float32)
+
+        def transfer(i):
+            if rank == 0:
+                comm.send(sends[i], 1)
+            else:
+                recv.reset()
+                comm.recv(recv.buf, 0)
+            torch.cuda.synchronize()
+            if rank == 1 and not recv.holds(_pattern(torch, 0, count, torch.float32, i)):
+                res["wrong"].append(i)
+
+        def retired_close():
+            deadline = time.perf_counter() + 1.0
+            while True:
+                awaiting = comm.registration_stats()[2]  # (each look closes what has completed)
+                if awaiting == 0 or time.perf_counter() > deadline:
+                    return awaiting == 0
+
+        for i in range(nbuf):
+            transfer(i)
+            if i >= KEPT_CAP:  # the 65th and the 66th allocation each evicted the least recently used import
+                res["closed"].append(retired_close())
+        # buffers 0 and 1 were evicted; their mappings may still be closing when they are imported again
+        for i in (0, 1):
+            transfer(i)
+        res["closed"].append(retired_close())
+        res["err"] = comm.device_error()
+        comm.barrier()
+        comm.destroy()
+        if rank == 0:
+            del sends
+            for b in bufs:
+                b.free()
+        q.put((rank, res, None))
+    except Exception:
+        q.put((rank, None, traceback.format_exc()))
+
+
+def test_recv_imports_beyond_the_kept_cap(built):
+    """66 send allocations from one peer against the receiver's cap of 64 kept imports: every transfer
+    is exact, the evicted imports close once their launches have completed (the retired-mapping count
+    reaches 0), and the evicted buffers arrive exact when sent again."""
+    n = 2
+    got = _spawn(_kept_cap_worker, n)
+    for rank in range(n):
+        assert got[rank] == {"wrong": [], "closed": [True, True, True], "err": 0}, (rank, got[rank])
+
+
 def _refusals_worker(rank, n, uid, q):
     try:
         import time
