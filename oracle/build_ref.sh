@@ -20,6 +20,15 @@ if [ "$FORCE" = 1 ] || ! { [ "$OUT/libref.so" -nt "$HERE/ref_harness.hip" ] && [
     -I"$REF/include" "$HERE/ref_harness.hip" -o "$OUT/libref.so"
   echo "built $OUT/libref.so"
 fi
+# The device primitive matrix (tests/cpp/test_device_primitives.hip) against the reference's own
+# include tree: the same source that tests/bin/test_device_primitives compiles against include/.
+# PRIMS_REFERENCE compiles out what the reference cannot run (see the program's header).
+PRIMS="$HERE/../tests/cpp/test_device_primitives.hip"
+if [ -f "$PRIMS" ] && { [ "$FORCE" = 1 ] || ! { [ "$OUT/test_device_primitives_ref" -nt "$PRIMS" ] && [ "$OUT/test_device_primitives_ref" -nt "$HERE/build_ref.sh" ]; }; }; then
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -x hip -O2 -std=c++17 -D__HIP_PLATFORM_AMD__ -DPRIMS_REFERENCE \
+    -I"$REF/include" "$PRIMS" -o "$OUT/test_device_primitives_ref"
+  echo "built $OUT/test_device_primitives_ref"
+fi
 # The reference's python benchmark kernels (python/mscclpp_benchmark/allreduce.cu), one code object
 # per TYPE (int, float, __half), whose allreduce2 ref_harness.hip's refBench2* run as n ranks on one
 # GPU.  int pins geometry, packet images and flags; float and __half also pin the order and the
