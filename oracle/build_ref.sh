@@ -29,6 +29,15 @@ if [ -f "$PRIMS" ] && { [ "$FORCE" = 1 ] || ! { [ "$OUT/test_device_primitives_r
     -I"$REF/include" "$PRIMS" -o "$OUT/test_device_primitives_ref"
   echo "built $OUT/test_device_primitives_ref"
 fi
+# The proxy-side matrix (tests/cpp/test_proxy_primitives.hip) against the reference's own include tree:
+# trigger images, ring laps and positions from the reference's fifo_device.hpp / port_channel_device.hpp
+# with no consumer at all.  PRIMS_REFERENCE compiles out the groups that need this library's host side.
+PROXY_PRIMS="$HERE/../tests/cpp/test_proxy_primitives.hip"
+if [ -f "$PROXY_PRIMS" ] && { [ "$FORCE" = 1 ] || ! { [ "$OUT/test_proxy_primitives_ref" -nt "$PROXY_PRIMS" ] && [ "$OUT/test_proxy_primitives_ref" -nt "$HERE/build_ref.sh" ]; }; }; then
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -x hip -O2 -std=c++17 -Wall -D__HIP_PLATFORM_AMD__ -DPRIMS_REFERENCE \
+    -I"$REF/include" "$PROXY_PRIMS" -o "$OUT/test_proxy_primitives_ref"
+  echo "built $OUT/test_proxy_primitives_ref"
+fi
 # The reference's python benchmark kernels (python/mscclpp_benchmark/allreduce.cu), one code object
 # per TYPE (int, float, __half), whose allreduce2 ref_harness.hip's refBench2* run as n ranks on one
 # GPU.  int pins geometry, packet images and flags; float and __half also pin the order and the
