@@ -209,6 +209,38 @@ typedef struct {
  * 4 GiB (more workgroups carry it), or the grid cannot be resident at once. */
 int mscclppAmdAllToAllLaunch(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdAllToAllSeg* segs,
                              int nblocks, int nthreads, uint64_t budgetTicks, void* stream);
+/* Small AllToAll / AllToAllv by one hop of LL8 packets through the ranks' LL scratch (kernels/
+ * alltoall_ll.hip): a push, nothing of the user's is registered and no token is
+ * exchanged.  One entry per peer q, in bytes: the rank sends `sendLen` bytes at `sendOff` of its input to
+ * rank q, and receives `recvLen` bytes from q at `recvOff` of its output (q == rank: a local copy).  What
+ * r sends q must be what q expects from r.  Segments may start at any byte and may be empty. */
+typedef struct {
+  uint64_t sendOff;
+  uint64_t sendLen;
+  uint64_t recvOff;
+  uint64_t recvLen;
+} mscclppAmdAllToAllLLSeg;
+/* Views as for mscclppAmdPullReduceLLLaunch (input = send buffer, output = receive buffer, scratch /
+ * peerScratch / flags shared with the other LL kernels, so calls may alternate).  table: host memory,
+ * [nviews][nranks], copied before the call returns.  The region stride comes from the largest length in
+ * `table`: with nviews == nranks that is the whole matrix; with fewer views every process must pass
+ * tables with the same largest length (the equal split does).  nblocks / nthreads <= 0: one lane per 8
+ * bytes of the largest segment, 256 lanes, 1 to 128 workgroups.
+ * 4 (nothing is launched, no device is touched): null fields, nranks outside 2..8, a rank twice, flags
+ * not 16-byte aligned, a length one view sends that the receiving view does not expect, a bad launch
+ * shape; 5: views whose scratchBytes differ or are below mscclppAmdAllToAllLLScratchRequired, a segment
+ * size the path does not carry, or a grid that cannot be resident at once. */
+int mscclppAmdAllToAllLLLaunch(const mscclppAmdRankView* views, int nviews, int nranks,
+                               const mscclppAmdAllToAllLLSeg* table, int nblocks, int nthreads, uint64_t budgetTicks,
+                               void* stream);
+/* Scratch bytes per rank that call needs when its largest segment has maxSegBytes: two halves of nranks
+ * regions of max(1, ceil(maxSegBytes / 8)) 16-byte units, each half rounded up to 256; 0: not carried. */
+size_t mscclppAmdAllToAllLLScratchRequired(int nranks, size_t maxSegBytes);
+/* 1 when ncclAllToAll / ncclAllToAllv send a call whose largest segment has maxSegBytes to the LL path,
+ * else 0: 0 < maxSegBytes <= the built-in bound of nranks, or <=
+ * MSCCLPP_AMD_A2A_LL_MAX_BYTES where that is set (0 disables the path, values above 1 MiB count as
+ * 1 MiB; read once; it must be equal on all ranks). */
+int mscclppAmdAllToAllTakesLL(int nranks, size_t maxSegBytes);
 /* Reduce to `root` by a zero-copy pull-reduce at the root (kernels/reduce.hip): the root reads
  * `bytes` of every rank's input (views[root].peerInput[q] = rank q's send buffer), reduces in ring
  * order root, root + 1, ..., root + n - 1 (mod n) with the arithmetic of the AllReduce kernels, and
@@ -337,7 +369,7 @@ int mscclppAmdTunedConfigSource(const char* collective, int nranks, size_t bytes
 // 3 reduce + all-gather stores issued, 4 end; zero-copy: 0 start, 1 entry handshake done, 2 reduce +
 // all-gather stores issued, 3 end; LL16: 0 start, 1 step 1 (puts), 2 step 2 (reduce + broadcast),
 // 3 step 3 (unpack) done; LL8: 0 start, 1 puts issued, 2 end; AllToAll: 0 start, 1 entry handshake
-// done, 2 segments stored, 3 end; Reduce: 0 start, 1 entry handshake done, 2 result stored (root),
+// done, 2 segments stored, 3 end; AllToAll LL: 0 start, 1 puts issued, 2 stored; Reduce: 0 start, 1 entry handshake done, 2 result stored (root),
 // 3 end; Send/Recv: 0 start, 1 readies posted, 2 receives stored, 3 dones seen; pull-reduce (MAX /
 // AVG): 0 start, 1 entry handshake done, 2 own range reduced, 3 peers' slices gathered (AllReduce
 // only), 4 end.  buf = NULL turns it off.  Returns 0,
@@ -383,6 +415,9 @@ int mscclppAmdCommRegistrationExchanges(ncclComm_t comm, uint64_t* allocationExc
                                         int* symmetricMemory);
 /* Collective calls of this communicator that took the LL path of mscclppAmdPullReduceLLLaunch. */
 int mscclppAmdCommPullLLCount(ncclComm_t comm, uint64_t* count);
+/* ncclAllToAll / ncclAllToAllv calls of this communicator that took the LL path of
+ * mscclppAmdAllToAllLLLaunch (counted apart from the above). */
+int mscclppAmdCommAllToAllLLCount(ncclComm_t comm, uint64_t* count);
 int mscclppAmdCommScratch(ncclComm_t comm, void** scratch, size_t* bytes);
 int mscclppAmdCommFlags(ncclComm_t comm, uint32_t** flags);
 /* Bootstrap all-gather of `bytes` per rank (host memory), for harnesses. */

@@ -109,6 +109,11 @@ class AllToAllSeg(ctypes.Structure):
     _fields_ = [("srcOff", ctypes.c_uint64), ("dstOff", ctypes.c_uint64), ("len", ctypes.c_uint64)]
 
 
+class AllToAllLLSeg(ctypes.Structure):
+    _fields_ = [("sendOff", ctypes.c_uint64), ("sendLen", ctypes.c_uint64), ("recvOff", ctypes.c_uint64),
+                ("recvLen", ctypes.c_uint64)]
+
+
 class SendRecvOp(ctypes.Structure):
     """mscclppAmdSendRecvOp: `bytes` move from `send` on rank `src` to `recv` on rank `dst` (the receiver pulls)."""
     _fields_ = [("src", ctypes.c_int32), ("dst", ctypes.c_int32), ("send", ctypes.c_void_p), ("recv", ctypes.c_void_p),
@@ -167,6 +172,10 @@ def lib():
         "ncclCommSplit": [vp, i32, i32, ctypes.POINTER(vp), vp],
         "mscclppAmdBroadcastLaunch": [ctypes.POINTER(RankView), i32, i32, sz, i32, i32, i32, u64, vp],
         "mscclppAmdAllToAllLaunch": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(AllToAllSeg), i32, i32, u64, vp],
+        "mscclppAmdAllToAllLLLaunch": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(AllToAllLLSeg), i32, i32, u64,
+                                       vp],
+        "mscclppAmdAllToAllTakesLL": [i32, sz],
+        "mscclppAmdCommAllToAllLLCount": [vp, ctypes.POINTER(ctypes.c_uint64)],
         "mscclppAmdReduceLaunch": [ctypes.POINTER(RankView), i32, i32, sz, i32, i32, i32, i32, i32, u64, vp],
         "ncclReduce": [vp, vp, sz, i32, i32, i32, vp, vp],
         "mscclppAmdPullReduceLaunch": [ctypes.POINTER(RankView), i32, i32, i32, sz, i32, i32, i32, i32, i32, u64, vp],
@@ -228,6 +237,8 @@ def lib():
     L.mscclppAmdScratchRequired.restype = sz
     L.mscclppAmdPullReduceLLScratchRequired.argtypes = [i32, i32, sz, i32, i32]
     L.mscclppAmdPullReduceLLScratchRequired.restype = sz
+    L.mscclppAmdAllToAllLLScratchRequired.argtypes = [i32, sz]
+    L.mscclppAmdAllToAllLLScratchRequired.restype = sz
     for name in ("mscclppAmdExecutionPlanName", "mscclppAmdExecutionPlanCollective"):
         getattr(L, name).argtypes = [vp]
         getattr(L, name).restype = ctypes.c_char_p
@@ -374,6 +385,7 @@ TRACE_PHASES = {
     "pull_reduce": ("entry_handshake", "pull_reduce", "exit_handshake"),
     "pull_allreduce": ("entry_handshake", "pull_reduce", "gather", "exit_handshake"),
     "pull_reduce_ll": ("put", "reduce"),
+    "alltoall_ll": ("put", "receive"),
 }
 
 
@@ -437,6 +449,18 @@ def pull_reduce_takes_ll(coll, nranks, nbytes):
 def pull_reduce_ll_scratch_required(coll, nranks, nbytes, dtype_code, op):
     """Scratch bytes per rank InProcessRanks.pull_reduce_ll needs for that call; 0: not carried."""
     return lib().mscclppAmdPullReduceLLScratchRequired(coll, nranks, nbytes, dtype_code, op)
+
+
+def alltoall_takes_ll(nranks, nbytes):
+    """Whether ncclAllToAll / ncclAllToAllv send a call whose largest segment has nbytes to the LL path:
+    the built-in bound of nranks, or MSCCLPP_AMD_A2A_LL_MAX_BYTES."""
+    return bool(lib().mscclppAmdAllToAllTakesLL(nranks, nbytes))
+
+
+def alltoall_ll_scratch_required(nranks, nbytes):
+    """Scratch bytes per rank InProcessRanks.all_to_all_ll needs when its largest segment has nbytes; 0: not
+    carried."""
+    return lib().mscclppAmdAllToAllLLScratchRequired(nranks, nbytes)
 
 
 class InProcessRanks:
@@ -532,6 +556,21 @@ class InProcessRanks:
         arr = self.views(sends, recvs)
         code = lib().mscclppAmdAllToAllLaunch(arr, n, n, tab, nblocks, nthreads, budget_ticks, stream_ptr(stream))
         check(code, "in-process all_to_all")
+
+    def all_to_all_ll(self, sends, recvs, segs=None, nblocks=0, nthreads=0, budget_ticks=500_000_000, stream=None):
+        """all_to_all for small segments by one hop of LL8 packets through the ranks' LL scratch
+        (mscclppAmdAllToAllLLLaunch): the same `segs` and the same bytes, a push, no handshake."""
+        n = self.n
+        if segs is None:
+            blk = sends[0].numel() * sends[0].element_size() // n
+            segs = [[(r * blk, p * blk, blk) for p in range(n)] for r in range(n)]
+        tab = (AllToAllLLSeg * (n * n))()
+        for r in range(n):
+            for q in range(n):  # what r sends q is what q receives from r
+                tab[r * n + q] = AllToAllLLSeg(segs[q][r][0], segs[q][r][2], segs[r][q][1], segs[r][q][2])
+        arr = self.views(sends, recvs)
+        code = lib().mscclppAmdAllToAllLLLaunch(arr, n, n, tab, nblocks, nthreads, budget_ticks, stream_ptr(stream))
+        check(code, "in-process all_to_all_ll")
 
     def reduce(self, inputs, outputs, root, op=SUM, nblocks=0, nthreads=0, budget_ticks=500_000_000, stream=None,
                accum=None):
@@ -857,6 +896,12 @@ class Communicator:
         c = ctypes.c_uint64()
         check(lib().mscclppAmdCommPullLLCount(self.comm, ctypes.byref(c)), "pull LL count")
         return c.value
+
+    def a2a_ll_count(self):
+        """ncclAllToAll / ncclAllToAllv calls of this communicator that took the LL path (alltoall_takes_ll)."""
+        c = ctypes.c_uint64()
+        check(lib().mscclppAmdCommAllToAllLLCount(self.comm, ctypes.byref(c)), "mscclppAmdCommAllToAllLLCount")
+        return int(c.value)
 
     def destroy(self):
         if self.comm:

@@ -185,8 +185,28 @@ int ncclComm::broadcast(const void* send, void* recv, size_t bytes, int root, in
 }
 
 int ncclComm::allToAll(const void* send, void* recv, const mscclppAmdAllToAllSeg* segs, int nblocks, hipStream_t stream,
-                       const SendIdent* idents) {
+                       const SendIdent* idents, const mscclppAmdAllToAllLLSeg* ll, uint64_t maxSeg) {
   std::lock_guard<std::mutex> lk(mu);
+  // Small exchanges: one hop of LL8 packets through the LL scratch (kernels/alltoall_ll.hip; DESIGN.md
+  // §17h) -- nothing is registered and no token is exchanged.  The rule is a function of (nranks,
+  // maxSeg) and the environment, so every rank decides alike.  Under capture a scratch that would have
+  // to grow cannot (ensure); such a call takes the pull path instead -- the capture state and llBytes
+  // are the same on every rank.
+  if (ll && alltoallTakesLL(nranks, maxSeg)) {
+    const size_t need = alltoallLLScratchRequired(nranks, maxSeg);
+    if (need && (need <= llBytes || !streamCapturing(stream))) {
+      mappings.beginLaunch();
+      mscclppAmdRankView v = baseView(send, recv);
+      ensure(llScratch, llBytes, peerLL, need, stream);
+      v.scratch = llScratch;
+      v.scratchBytes = llBytes;
+      for (int r = 0; r < nranks; ++r) v.peerScratch[r] = peerLL[r];
+      const int rc = launchAllToAllLL(&v, 1, nranks, ll, maxSeg, 0, 0, spinBudgetTicks(), stream);
+      mappings.recordUses(stream, device);
+      if (rc == 0) ++a2aLLCount;
+      return rc;
+    }
+  }
   mscclppAmdRankView v = pullView(send, recv, stream, idents);
   const int rc = launchAllToAll(&v, 1, nranks, segs, nblocks, 0, spinBudgetTicks(), stream);
   mappings.recordUses(stream, device);

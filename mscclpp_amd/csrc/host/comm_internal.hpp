@@ -371,6 +371,7 @@ struct ncclComm {
   std::array<std::vector<Lease>, MSCCLPP_AMD_MAX_RANKS> p2pImports;
   static constexpr int kP2pTag = 3;  // outside the 4k+0..2 tag spaces of core.cpp (memTag, connTag, semTag)
   uint64_t pullLLCount = 0;  // collective calls that took pullReduce's LL path
+  uint64_t a2aLLCount = 0;   // ncclAllToAll / ncclAllToAllv calls that took allToAll's LL path
   // PreMulSum handles: a handle's value is ncclNumOps + its slot; a destroyed slot is taken again by
   // the next create.  With a vendor communicator the handles are the vendor library's and this
   // table stays empty.
@@ -470,8 +471,11 @@ struct ncclComm {
   // rank's own receive buffer, which needs no registration.  nblocks: the same on every rank.
   // idents: every rank's sendIdent of this call where the caller gathered them (AllToAllv,
   // registerPaired); null: registerOutput, the other collectives' contract of matching buffers.
+  // ll / maxSeg: the same call as the table of kernels/alltoall_ll.hip (ll[q] = what this rank sends to and
+  // receives from rank q) and the largest segment of the whole matrix, which every rank knows alike.  A
+  // call the rule sends there (alltoallTakesLL) registers nothing and builds no pullView.
   int allToAll(const void* send, void* recv, const mscclppAmdAllToAllSeg* segs, int nblocks, hipStream_t stream,
-               const SendIdent* idents = nullptr);
+               const SendIdent* idents = nullptr, const mscclppAmdAllToAllLLSeg* ll = nullptr, uint64_t maxSeg = 0);
   // Reduce to `root` by a zero-copy pull-reduce at the root (kernels/reduce.hip).  The send buffer is
   // what the root reads, so it is the one registered, on every rank (collective on first use, cached
   // per allocation, pinned under capture: the matching-buffer contract of AllToAll); the result is

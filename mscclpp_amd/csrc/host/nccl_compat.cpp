@@ -435,9 +435,13 @@ ncclResult_t ncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, nc
     if (vendorComm(comm) && vendorNccl()->AllToAll && forcedFallback("alltoall"))
       return (int)vendorNccl()->AllToAll(sendbuff, recvbuff, count, datatype, vendorComm(comm), stream);
     mscclppAmdAllToAllSeg segs[MSCCLPP_AMD_MAX_RANKS];
-    for (size_t p = 0; p < n; ++p) segs[p] = {(uint64_t)comm->rank * bytes, p * bytes, bytes};
+    mscclppAmdAllToAllLLSeg ll[MSCCLPP_AMD_MAX_RANKS];
+    for (size_t p = 0; p < n; ++p) {
+      segs[p] = {(uint64_t)comm->rank * bytes, p * bytes, bytes};
+      ll[p] = {p * bytes, bytes, p * bytes, bytes};
+    }
     return comm->allToAll(sendbuff, recvbuff, segs, mscclpp_amd::alltoallDefaultBlocks(n * bytes),
-                          (hipStream_t)stream);
+                          (hipStream_t)stream, nullptr, ll, bytes);
   });
 }
 
@@ -510,7 +514,7 @@ ncclResult_t ncclAllToAllv(const void* sendbuff, const size_t sendcounts[], cons
       std::lock_guard<std::mutex> lk(comm->mu);
       comm->boot->allGather(&mine, all.data(), sizeof(Row));
     }
-    uint64_t mostRecv = 0;
+    uint64_t mostRecv = 0, maxSeg = 0;  // maxSeg: the largest segment of the matrix, for the LL path
     for (int r = 0; r < n; ++r) {
       if (!all[(size_t)r].ok) {
         warn("ncclAllToAllv: rank " + std::to_string(r) + " passed invalid arguments");
@@ -524,16 +528,21 @@ ncclResult_t ncclAllToAllv(const void* sendbuff, const size_t sendcounts[], cons
           return (int)ncclInvalidArgument;
         }
         sum += all[(size_t)r].recv[p] * tb;
+        maxSeg = std::max<uint64_t>(maxSeg, all[(size_t)r].recv[p] * tb);
       }
       mostRecv = std::max(mostRecv, sum);
     }
     mscclppAmdAllToAllSeg segs[MSCCLPP_AMD_MAX_RANKS];
-    for (int p = 0; p < n; ++p)
+    mscclppAmdAllToAllLLSeg ll[MSCCLPP_AMD_MAX_RANKS];
+    for (int p = 0; p < n; ++p) {
       segs[p] = {all[(size_t)p].sdis[me] * tb, (uint64_t)rdispls[p] * tb, (uint64_t)recvcounts[p] * tb};
+      ll[p] = {(uint64_t)sdispls[p] * tb, (uint64_t)sendcounts[p] * tb, (uint64_t)rdispls[p] * tb,
+               (uint64_t)recvcounts[p] * tb};
+    }
     ncclComm::SendIdent idents[MSCCLPP_AMD_MAX_RANKS];
     for (int r = 0; r < n; ++r) idents[r] = all[(size_t)r].ident;
     return comm->allToAll(sendbuff, recvbuff, segs, mscclpp_amd::alltoallDefaultBlocks(mostRecv), (hipStream_t)stream,
-                          idents);
+                          idents, ll, maxSeg);
   });
 }
 
@@ -786,6 +795,43 @@ size_t mscclppAmdPullReduceLLScratchRequired(int coll, int nranks, size_t bytes,
 
 int mscclppAmdPullReduceTakesLL(int coll, int nranks, size_t bytes) {
   return mscclpp_amd::pullReduceTakesLL(coll, nranks, bytes) ? 1 : 0;
+}
+
+// Small AllToAll(v) by one hop of LL8 packets, for in-process ranks (and the one-view form the NCCL entry
+// points launch): everything is checked before a device is touched; a refusal launches nothing.  (The
+// table, the rank count and the lengths between views: launchAllToAllLL.)
+int mscclppAmdAllToAllLLLaunch(const mscclppAmdRankView* views, int nviews, int nranks,
+                               const mscclppAmdAllToAllLLSeg* table, int nblocks, int nthreads, uint64_t budgetTicks,
+                               void* stream) {
+  return guarded([&] {
+    ViewNeeds needs;
+    needs.all = kViewInput | kViewOutput | kViewScratch | kViewFlags | kViewErr | kViewPeerScratch;
+    if (!table || !viewsValid(views, nviews, nranks, needs)) return (int)ncclInvalidArgument;
+    unsigned seen = 0;
+    for (int i = 0; i < nviews; ++i) {
+      const mscclppAmdRankView& v = views[i];
+      if ((seen >> v.rank) & 1u) return (int)ncclInvalidArgument;  // no rank twice
+      seen |= 1u << v.rank;
+      if ((uintptr_t)v.flags % 16) return (int)ncclInvalidArgument;  // 16-byte flag refresh
+    }
+    return mscclpp_amd::launchAllToAllLL(views, nviews, nranks, table, ~0ull, nblocks, nthreads,
+                                         budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream);
+  });
+}
+
+size_t mscclppAmdAllToAllLLScratchRequired(int nranks, size_t maxSegBytes) {
+  return mscclpp_amd::alltoallLLScratchRequired(nranks, maxSegBytes);
+}
+
+int mscclppAmdAllToAllTakesLL(int nranks, size_t maxSegBytes) {
+  return mscclpp_amd::alltoallTakesLL(nranks, maxSegBytes) ? 1 : 0;
+}
+
+int mscclppAmdCommAllToAllLLCount(ncclComm_t comm, uint64_t* count) {
+  if (!comm || !count) return ncclInvalidArgument;
+  std::lock_guard<std::mutex> lk(comm->mu);
+  *count = comm->a2aLLCount;
+  return ncclSuccess;
 }
 
 int mscclppAmdCommPullLLCount(ncclComm_t comm, uint64_t* count) {

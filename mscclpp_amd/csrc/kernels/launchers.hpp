@@ -22,6 +22,10 @@ int launchBroadcast(const mscclppAmdRankView* views, int nviews, int nranks, siz
 int launchAllToAll(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdAllToAllSeg* segs,
                    int nblocks, int nthreads, uint64_t budget, hipStream_t s);
 int alltoallDefaultBlocks(uint64_t maxRecvBytes);
+int launchAllToAllLL(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdAllToAllLLSeg* table,
+                     uint64_t maxSeg, int nblocks, int nthreads, uint64_t budget, hipStream_t s);
+size_t alltoallLLScratchRequired(int nranks, size_t maxSegBytes);
+bool alltoallTakesLL(int nranks, size_t maxSegBytes);
 int launchReduce(const mscclppAmdRankView* views, int nviews, int nranks, size_t bytes, int dtype, int op, int root,
                  int nblocks, int nthreads, uint64_t budget, hipStream_t s);
 int reduceDefaultBlocks(uint64_t bytes);

@@ -14,6 +14,13 @@ With nviews > 1 the AllToAll's segment table travels through a one-workgroup fil
 of each launch (the one-rank-per-process launch passes it by value), which the time includes.
 
     python tools/alltoall_perf.py        (writes profiles/alltoall_perf_inprocess_n8.json, or $OUT)
+
+MODE=ll: the small-message sweep behind the LL cutover.  Per segment size 8 B ... 1 MiB
+(equal split, NRANKS in-process ranks), the pull kernel and the LL kernel of kernels/alltoall_ll.hip at
+their default shapes, alternating in one run, each captured in a HIP graph of K calls, median of ROUNDS
+rounds; the bound is the largest swept size up to which the LL median is at or below the pull median.
+
+    MODE=ll NRANKS=4 python tools/alltoall_perf.py   (writes profiles/alltoall_ll_perf_inprocess_n4.json)
 """
 import ctypes
 import json
@@ -60,6 +67,64 @@ def blocks_for(S):
     want = (S + (256 << 10) - 1) // (256 << 10)
     return min(max(want, 8), 128)
 
+
+def ll_sweep():
+    sizes = [int(x) for x in os.environ["SIZES"].split(",")] if "SIZES" in os.environ else [8 << k for k in range(18)]
+    need = m.alltoall_ll_scratch_required(N, max(sizes))
+    ranks = m.InProcessRanks(N, need)
+    out_rows, bound, beaten = [], 0, False
+    for seg in sizes:
+        S = seg * N
+        sends = [torch.randint(0, 256, (S,), dtype=torch.uint8, device=dev) for _ in range(N)]
+        outs = {k: [torch.full((S,), 0xA5, dtype=torch.uint8, device=dev) for _ in range(N)] for k in ("pull", "ll")}
+
+        def pull():
+            ranks.all_to_all(sends, outs["pull"], budget_ticks=300_000_000, stream=torch.cuda.current_stream())
+
+        def ll():
+            ranks.all_to_all_ll(sends, outs["ll"], budget_ticks=300_000_000, stream=torch.cuda.current_stream())
+
+        pull(), ll()
+        torch.cuda.synchronize()
+        ok = ranks.errors() == [0] * N and all(
+            torch.equal(outs[k][r][p * seg:(p + 1) * seg], sends[p][r * seg:(r + 1) * seg])
+            for k in outs for r in range(N) for p in range(N))
+        calls, replays = (10, 5) if seg >= (256 << 10) else (50, 10)
+        t = {"pull": [], "ll": []}
+        for _ in range(ROUNDS):
+            for name, fn in (("pull", pull), ("ll", ll)):
+                t[name].append(graph_us(fn, calls, replays))
+        us = {k: float(np.median(v)) for k, v in t.items()}
+        wins = us["ll"] <= us["pull"]
+        if wins and not beaten:
+            bound = seg
+        beaten = beaten or not wins
+        row = {"segment_bytes": seg, "correct": bool(ok), "errors": ranks.errors(), "graph_calls": calls,
+               "replays": replays, "rounds": ROUNDS, "pull_us": round(us["pull"], 2), "ll_us": round(us["ll"], 2),
+               "pull_us_all": [round(x, 2) for x in t["pull"]], "ll_us_all": [round(x, 2) for x in t["ll"]],
+               "ll_at_or_below_pull": bool(wins)}
+        out_rows.append(row)
+        print(row, flush=True)
+        del sends, outs
+    with m.PhaseTrace() as tr:
+        x = [torch.randint(0, 256, (N * 4096,), dtype=torch.uint8, device=dev) for _ in range(N)]
+        ranks.all_to_all_ll(x, [torch.empty_like(t) for t in x])
+        torch.cuda.synchronize()
+    res = {"tool": "tools/alltoall_perf.py MODE=ll", "fabric_free": True, "gpus": 1, "nranks": N,
+           "note": "in-process ranks on one GPU: no xGMI byte is priced; graph-captured, median of rounds; the "
+                   "in-process pull launch includes its one-workgroup table fill kernel, the LL launch carries its "
+                   "table by value", "bound_bytes": bound, "phases_rank0_4096": tr.phases("alltoall_ll", view=0),
+           "rows": out_rows}
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = os.environ.get("OUT", os.path.join(root, "profiles", f"alltoall_ll_perf_inprocess_n{N}.json"))
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    json.dump(res, open(out, "w"), indent=1)
+    print({"nranks": N, "bound_bytes": bound}, flush=True)
+
+
+if os.environ.get("MODE") == "ll":
+    ll_sweep()
+    sys.exit(0)
 
 rows = []
 for S in SIZES:
