@@ -314,6 +314,30 @@ size_t mscclppAmdPullReduceLLScratchRequired(int coll, int nranks, size_t bytes,
  * §17g), or <= MSCCLPP_AMD_PULL_LL_MAX_BYTES where that is set (one bound for both collectives, 0
  * disables the path, values above 1 MiB count as 1 MiB; read once; it must be equal on all ranks). */
 int mscclppAmdPullReduceTakesLL(int coll, int nranks, size_t bytes);
+/* Fused small AllReduce (sum) + residual add + RMSNorm of fp16 / bf16 rows by one hop of LL8 packets
+ * (kernels/allreduce_rmsnorm_ll.hip).  Every rank holds x[rows][cols] (view.input), a
+ * replicated residual[rows][cols] or none, a replicated gamma[cols] and eps; every rank ends with
+ *   s = x_0 + ... + x_{n-1} (fp32, rank order), zq = (DT)(s + residual) -> resOut (no residual: (DT)s, not
+ *   stored), ms = sum_j zq_j^2 / cols, y_j = (DT)((zq_j * rsqrt(ms + eps)) * gamma_j) -> view.output.
+ * Views as for mscclppAmdPullReduceLLLaunch (input, output, scratch, peerScratch[q], flags, err; the flags
+ * and the scratch are shared with the other LL kernels, so calls may alternate).  residual / resOut / gamma:
+ * host arrays with one entry per view; residual and resOut may both be NULL, or hold NULL on every view.
+ * In place is carried as output == input and resOut[i] == residual[i].  dtype: MSCCLPP_AMD_F16 or _BF16.
+ * nblocks <= 0: min(rows, 64) workgroups, each owning whole rows; nthreads <= 0: 256 lanes, 512 when
+ * cols > 8192; a lane owns at most 8 units of 4 elements of a row, so cols <= 32 * nthreads.
+ * 4 (nothing is launched, no device is touched): null views / x / y / gamma, nranks outside 2..8, rows of
+ * 0, cols of 0 or no multiple of 4 or above 32 * nthreads, another dtype, a pointer that is not 8-byte
+ * aligned, resOut without residual or the reverse, buffers that overlap otherwise than by the two in-place
+ * forms, a bad launch shape; 5: rows * cols * 2 above MSCCLPP_AMD_ARNORM_MAX_BYTES (default and at most
+ * 1 MiB; 0 refuses every call; read once), views whose scratchBytes differ or are below
+ * mscclppAmdAllReduceRmsNormScratchRequired, or a grid that cannot be resident at once. */
+int mscclppAmdAllReduceRmsNormLaunch(const mscclppAmdRankView* views, int nviews, int nranks,
+                                     const void* const* residual, void* const* resOut, const void* const* gamma,
+                                     size_t rows, size_t cols, int dtype, float eps, int nblocks, int nthreads,
+                                     uint64_t budgetTicks, void* stream);
+/* Scratch bytes per rank that call needs (two halves of nranks regions of rows * cols / 4 16-byte units,
+ * each half rounded up to 256); 0: the call is not carried at any setting. */
+size_t mscclppAmdAllReduceRmsNormScratchRequired(int nranks, size_t rows, size_t cols, int dtype);
 /* Send / Recv by a zero-copy pull (kernels/sendrecv.hip): one launch runs a table of point-to-point
  * operations, in table order.  An operation moves `bytes` from `send` on rank `src` to `recv` on
  * rank `dst`: the receiver reads `send` -- the address at which the view of rank `dst` has the
@@ -369,7 +393,7 @@ int mscclppAmdTunedConfigSource(const char* collective, int nranks, size_t bytes
 // 3 reduce + all-gather stores issued, 4 end; zero-copy: 0 start, 1 entry handshake done, 2 reduce +
 // all-gather stores issued, 3 end; LL16: 0 start, 1 step 1 (puts), 2 step 2 (reduce + broadcast),
 // 3 step 3 (unpack) done; LL8: 0 start, 1 puts issued, 2 end; AllToAll: 0 start, 1 entry handshake
-// done, 2 segments stored, 3 end; AllToAll LL: 0 start, 1 puts issued, 2 stored; Reduce: 0 start, 1 entry handshake done, 2 result stored (root),
+// done, 2 segments stored, 3 end; AllToAll LL: 0 start, 1 puts issued, 2 stored; AllReduce+RMSNorm (of a workgroup's last row): 0 start, 1 puts issued, 2 reduced, 3 normalised; Reduce: 0 start, 1 entry handshake done, 2 result stored (root),
 // 3 end; Send/Recv: 0 start, 1 readies posted, 2 receives stored, 3 dones seen; pull-reduce (MAX /
 // AVG): 0 start, 1 entry handshake done, 2 own range reduced, 3 peers' slices gathered (AllReduce
 // only), 4 end.  buf = NULL turns it off.  Returns 0,
@@ -383,6 +407,14 @@ int mscclppAmdCommAllReduce(ncclComm_t comm, const void* sendbuff, void* recvbuf
  * element type; ncclFloat16 / ncclFloat32 for FP8 buffers). */
 int mscclppAmdCommAllReduceAccum(ncclComm_t comm, const void* sendbuff, void* recvbuff, size_t count, int ncclDtype,
                                  int ncclOp, int accumNcclDtype, int algo, int nblocks, int nthreads, void* stream);
+/* The fused AllReduce + residual add + RMSNorm of mscclppAmdAllReduceRmsNormLaunch on this communicator's LL
+ * scratch and flags: x, y (and residual, resOut: both or neither) are [rows][cols] of ncclFloat16 /
+ * ncclBfloat16, gamma is [cols]; y == x and resOut == residual are carried.  Nothing is registered, no
+ * algorithm is selected and no host traffic runs; every rank must make the same call.  Refusals as for the
+ * launch entry point; also ncclInvalidArgument on a one-rank communicator, and ncclInvalidUsage under
+ * stream capture when the scratch would have to grow. */
+int mscclppAmdCommAllReduceRmsNorm(ncclComm_t comm, const void* x, void* y, const void* residual, void* resOut,
+                                   const void* gamma, size_t rows, size_t cols, int ncclDtype, float eps, void* stream);
 /* Reduce-type code (MSCCLPP_AMD_*) for an ncclDataType_t and accumulation type (-1 = AUTO), or -1. */
 int mscclppAmdReduceType(int ncclDtype, int accumNcclDtype);
 int mscclppAmdCommBarrier(ncclComm_t comm);

@@ -175,6 +175,9 @@ def lib():
         "mscclppAmdAllToAllLLLaunch": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(AllToAllLLSeg), i32, i32, u64,
                                        vp],
         "mscclppAmdAllToAllTakesLL": [i32, sz],
+        "mscclppAmdAllReduceRmsNormLaunch": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                             ctypes.POINTER(vp), sz, sz, i32, ctypes.c_float, i32, i32, u64, vp],
+        "mscclppAmdCommAllReduceRmsNorm": [vp, vp, vp, vp, vp, vp, sz, sz, i32, ctypes.c_float, vp],
         "mscclppAmdCommAllToAllLLCount": [vp, ctypes.POINTER(ctypes.c_uint64)],
         "mscclppAmdReduceLaunch": [ctypes.POINTER(RankView), i32, i32, sz, i32, i32, i32, i32, i32, u64, vp],
         "ncclReduce": [vp, vp, sz, i32, i32, i32, vp, vp],
@@ -239,6 +242,8 @@ def lib():
     L.mscclppAmdPullReduceLLScratchRequired.restype = sz
     L.mscclppAmdAllToAllLLScratchRequired.argtypes = [i32, sz]
     L.mscclppAmdAllToAllLLScratchRequired.restype = sz
+    L.mscclppAmdAllReduceRmsNormScratchRequired.argtypes = [i32, sz, sz, i32]
+    L.mscclppAmdAllReduceRmsNormScratchRequired.restype = sz
     for name in ("mscclppAmdExecutionPlanName", "mscclppAmdExecutionPlanCollective"):
         getattr(L, name).argtypes = [vp]
         getattr(L, name).restype = ctypes.c_char_p
@@ -386,6 +391,7 @@ TRACE_PHASES = {
     "pull_allreduce": ("entry_handshake", "pull_reduce", "gather", "exit_handshake"),
     "pull_reduce_ll": ("put", "reduce"),
     "alltoall_ll": ("put", "receive"),
+    "allreduce_rms_norm": ("put", "reduce", "normalise"),
 }
 
 
@@ -461,6 +467,22 @@ def alltoall_ll_scratch_required(nranks, nbytes):
     """Scratch bytes per rank InProcessRanks.all_to_all_ll needs when its largest segment has nbytes; 0: not
     carried."""
     return lib().mscclppAmdAllToAllLLScratchRequired(nranks, nbytes)
+
+
+def _rms_norm_tensors(x, y, residual, res_out, gamma):
+    """The raw pointers the fused AllReduce + RMSNorm entry points take say nothing of shape, type or layout:
+    x is 2-D, y / residual / res_out (where given) have its shape, gamma has its columns, all have its dtype
+    and are contiguous -- or the call is refused here as ncclInvalidArgument."""
+    ok = x is not None and gamma is not None and y is not None and x.dim() == 2 and tuple(gamma.shape) == (x.shape[1],)
+    for t in (x, y, residual, res_out, gamma) if ok else ():
+        ok = ok and (t is None or (t.dtype == x.dtype and t.is_contiguous() and (t is gamma or t.shape == x.shape)))
+    if not ok:
+        raise MscclppError(4, "all_reduce_rms_norm: tensors of one dtype, contiguous, x's shape, gamma of its columns")
+
+
+def all_reduce_rms_norm_scratch_required(nranks, rows, cols, dtype_code):
+    """Scratch bytes per rank InProcessRanks.all_reduce_rms_norm needs for [rows][cols]; 0: not carried."""
+    return lib().mscclppAmdAllReduceRmsNormScratchRequired(nranks, rows, cols, dtype_code)
 
 
 class InProcessRanks:
@@ -637,6 +659,24 @@ class InProcessRanks:
                                                   budget_ticks, stream_ptr(stream), imm, ptrs)
         check(code, "in-process pull_reduce_ll")
 
+    def all_reduce_rms_norm(self, xs, ys, gammas, residuals=None, res_outs=None, eps=1e-6, nblocks=0, nthreads=0,
+                            budget_ticks=500_000_000, stream=None):
+        """Fused AllReduce + residual add + RMSNorm by one hop of LL8 packets (mscclppAmdAllReduceRmsNormLaunch):
+        xs[r] is rank r's [rows][cols] float16 / bfloat16 term; every rank ends with res_outs[r] = the sum of the
+        xs in rank order (fp32) plus residuals[r], rounded once, and ys[r] = that row-normalised (RMSNorm with
+        eps) times gammas[r] ([cols]).  Without residuals nothing is stored for the sum.  ys[r] may be xs[r] and
+        res_outs[r] may be residuals[r]."""
+        for r in range(self.n):
+            _rms_norm_tensors(xs[r], ys[r], residuals and residuals[r], res_outs and res_outs[r], gammas[r])
+            if xs[r].shape != xs[0].shape or xs[r].dtype != xs[0].dtype:
+                raise MscclppError(4, "all_reduce_rms_norm: the ranks' tensors differ in shape or dtype")
+        rows, cols = xs[0].shape
+        ptrs = lambda ts: None if ts is None else (ctypes.c_void_p * self.n)(*[None if t is None else t.data_ptr() for t in ts])
+        code = lib().mscclppAmdAllReduceRmsNormLaunch(self.views(xs, ys), self.n, self.n, ptrs(residuals), ptrs(res_outs),
+                                                      ptrs(gammas), rows, cols, DTYPE_CODES.get(xs[0].dtype, -1), eps,
+                                                      nblocks, nthreads, budget_ticks, stream_ptr(stream))
+        check(code, "in-process all_reduce_rms_norm")
+
     def send_recv(self, ops, nblocks=0, nthreads=0, budget_ticks=500_000_000, stream=None):
         """ncclSend / ncclRecv (a whole group) for in-process ranks, one launch.  ops: (src, dst, send,
         recv) in table order -- `send` on rank src (a tensor, read in place by rank dst) lands in
@@ -729,6 +769,23 @@ class Communicator:
                                                  nblocks, nthreads, stream_ptr(stream))
         check(code, "ncclAllReduce")
         return recv
+
+    def all_reduce_rms_norm(self, x, gamma, y=None, residual=None, res_out=None, eps=1e-6, stream=None):
+        """Fused AllReduce (sum over the ranks, fp32, rank order) + residual add + RMSNorm of a [rows][cols]
+        float16 / bfloat16 tensor (mscclppAmdCommAllReduceRmsNorm): res_out = the sum plus `residual`, rounded
+        once; y = res_out row-normalised with eps, times gamma ([cols]).  y defaults to x (in place) and, with a
+        residual, res_out to the residual.  Without a residual the sum itself is normalised and not stored.
+        Every rank makes the same call; returns (y, res_out)."""
+        y = x if y is None else y
+        if residual is not None and res_out is None:
+            res_out = residual
+        _rms_norm_tensors(x, y, residual, res_out, gamma)
+        rows, cols = x.shape
+        ptr = lambda t: ctypes.c_void_p(None if t is None else t.data_ptr())
+        check(lib().mscclppAmdCommAllReduceRmsNorm(self.comm, ptr(x), ptr(y), ptr(residual), ptr(res_out), ptr(gamma),
+                                                   rows, cols, NCCL_DTYPES.get(x.dtype, -1), eps, stream_ptr(stream)),
+              "mscclppAmdCommAllReduceRmsNorm")
+        return y, res_out
 
     def reduce_scatter(self, send, recv, op="sum", stream=None):
         """ncclReduceScatter(send, recv, recvcount, dtype, op, comm, stream)."""

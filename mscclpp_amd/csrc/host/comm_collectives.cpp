@@ -261,6 +261,36 @@ int ncclComm::pullReduce(int coll, const void* send, void* recv, size_t bytes, i
   return rc;
 }
 
+int ncclComm::allReduceRmsNorm(const void* x, void* y, const void* residual, void* resOut, const void* gamma,
+                               size_t rows, size_t cols, int dtype, float eps, hipStream_t stream) {
+  std::lock_guard<std::mutex> lk(mu);
+  mscclppAmdRankView v = baseView(x, y);
+  const void* const* res = residual || resOut ? &residual : nullptr;
+  void* const* ro = residual || resOut ? &resOut : nullptr;
+  // A call with a bad argument, or of a size the path does not carry, is refused before the communicator's
+  // bookkeeping and before any device call; the answer depends on the arguments alone.
+  int nthreads = 0;
+  if (const int rc = allReduceRmsNormCheck(&v, 1, nranks, res, ro, &gamma, rows, cols, dtype, 0, nthreads, nullptr))
+    return rc;
+  // A guard only: 64 MiB of LL scratch are held from init and the largest call carried needs 32 MiB, so
+  // no call grows it today.  Should the initial scratch ever shrink, a captured call must not re-allocate
+  // (ensure); llBytes and the capture state are the same on every rank, so all refuse alike.
+  const size_t need = allReduceRmsNormScratchRequired(nranks, rows, cols, dtype);
+  if (need > llBytes && streamCapturing(stream)) {
+    warn("AllReduce+RMSNorm under stream capture: the LL scratch would have to grow");
+    return ncclInvalidUsage;
+  }
+  mappings.beginLaunch();
+  ensure(llScratch, llBytes, peerLL, need, stream);
+  v.scratch = llScratch;
+  v.scratchBytes = llBytes;
+  for (int r = 0; r < nranks; ++r) v.peerScratch[r] = peerLL[r];
+  const int rc = launchAllReduceRmsNorm(&v, 1, nranks, res, ro, &gamma, rows, cols, dtype, eps, 0, 0, spinBudgetTicks(),
+                                        stream);
+  mappings.recordUses(stream, device);
+  return rc;
+}
+
 ncclRedOp_t ncclComm::preMulCreate(const PreMulOp& e) {
   std::lock_guard<std::mutex> lk(mu);
   size_t slot = 0;

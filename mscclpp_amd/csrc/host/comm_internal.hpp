@@ -492,6 +492,12 @@ struct ncclComm {
   // non-null, the element of the element type it points to in device memory when the kernel runs.
   int pullReduce(int coll, const void* send, void* recv, size_t bytes, int dtype, int op, int root, hipStream_t stream,
                  float scale = 0.0f, const void* scalePtr = nullptr);
+  // Fused small AllReduce + residual add + RMSNorm (kernels/allreduce_rmsnorm_ll.hip), shaped
+  // like pullReduce's LL branch: the LL scratch and flags, nothing registered, no bootstrap traffic.  There
+  // is no other path: a call the kernel does not carry, or whose scratch would have to grow under capture,
+  // is refused.  dtype: MSCCLPP_AMD_F16 / _BF16.
+  int allReduceRmsNorm(const void* x, void* y, const void* residual, void* resOut, const void* gamma, size_t rows,
+                       size_t cols, int dtype, float eps, hipStream_t stream);
   ncclRedOp_t preMulCreate(const PreMulOp& e);
   // The live entry of `op` (a copy: the caller launches after the lock is dropped, and the handle may
   // be destroyed as soon as the collective call has returned), or false.

@@ -827,6 +827,44 @@ int mscclppAmdAllToAllTakesLL(int nranks, size_t maxSegBytes) {
   return mscclpp_amd::alltoallTakesLL(nranks, maxSegBytes) ? 1 : 0;
 }
 
+// Fused small AllReduce + residual add + RMSNorm, for in-process ranks (and the one-view form the
+// communicator launches): the views' plumbing is checked here, everything about the buffers and the shape
+// by launchAllReduceRmsNorm, all before a device is touched; a refusal launches nothing.
+int mscclppAmdAllReduceRmsNormLaunch(const mscclppAmdRankView* views, int nviews, int nranks,
+                                     const void* const* residual, void* const* resOut, const void* const* gamma,
+                                     size_t rows, size_t cols, int dtype, float eps, int nblocks, int nthreads,
+                                     uint64_t budgetTicks, void* stream) {
+  return guarded([&] {
+    ViewNeeds needs;
+    needs.all = kViewInput | kViewOutput | kViewScratch | kViewFlags | kViewErr | kViewPeerScratch;
+    if (!gamma || !viewsValid(views, nviews, nranks, needs)) return (int)ncclInvalidArgument;
+    unsigned seen = 0;
+    for (int i = 0; i < nviews; ++i) {
+      const mscclppAmdRankView& v = views[i];
+      if ((seen >> v.rank) & 1u) return (int)ncclInvalidArgument;  // no rank twice
+      seen |= 1u << v.rank;
+      if ((uintptr_t)v.flags % 16) return (int)ncclInvalidArgument;  // 16-byte flag refresh
+    }
+    return mscclpp_amd::launchAllReduceRmsNorm(views, nviews, nranks, residual, resOut, gamma, rows, cols, dtype, eps,
+                                               nblocks, nthreads, budgetTicks ? budgetTicks : spinBudgetTicks(),
+                                               (hipStream_t)stream);
+  });
+}
+
+size_t mscclppAmdAllReduceRmsNormScratchRequired(int nranks, size_t rows, size_t cols, int dtype) {
+  return mscclpp_amd::allReduceRmsNormScratchRequired(nranks, rows, cols, dtype);
+}
+
+int mscclppAmdCommAllReduceRmsNorm(ncclComm_t comm, const void* x, void* y, const void* residual, void* resOut,
+                                   const void* gamma, size_t rows, size_t cols, int ncclDtype, float eps, void* stream) {
+  return guarded([&] {
+    if (!comm || comm->nranks < 2) return (int)ncclInvalidArgument;  // (one rank: refused)
+    const int dt = ncclDtype == (int)ncclFloat16 ? MSCCLPP_AMD_F16 : ncclDtype == (int)ncclBfloat16 ? MSCCLPP_AMD_BF16 : -1;
+    if (dt < 0) return (int)ncclInvalidArgument;
+    return comm->allReduceRmsNorm(x, y, residual, resOut, gamma, rows, cols, dt, eps, (hipStream_t)stream);
+  });
+}
+
 int mscclppAmdCommAllToAllLLCount(ncclComm_t comm, uint64_t* count) {
   if (!comm || !count) return ncclInvalidArgument;
   std::lock_guard<std::mutex> lk(comm->mu);

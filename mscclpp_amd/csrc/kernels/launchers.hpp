@@ -38,6 +38,13 @@ int launchPullReduceLL(const mscclppAmdRankView* views, int nviews, int nranks, 
                        const void* const* scalePtrs);
 size_t pullReduceLLScratchRequired(int coll, int nranks, size_t bytes, int dtype, int op);
 bool pullReduceTakesLL(int coll, int nranks, size_t bytes);
+int launchAllReduceRmsNorm(const mscclppAmdRankView* views, int nviews, int nranks, const void* const* residual,
+                           void* const* resOut, const void* const* gamma, size_t rows, size_t cols, int dtype, float eps,
+                           int nblocks, int nthreads, uint64_t budget, hipStream_t s);
+int allReduceRmsNormCheck(const mscclppAmdRankView* views, int nviews, int nranks, const void* const* residual,
+                          void* const* resOut, const void* const* gamma, size_t rows, size_t cols, int dtype,
+                          int nblocks, int& nthreads, int* upl);
+size_t allReduceRmsNormScratchRequired(int nranks, size_t rows, size_t cols, int dtype);
 int launchSendRecv(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdSendRecvOp* ops, int nops,
                    int nblocks, int nthreads, uint64_t budget, hipStream_t s);
 int sendrecvDefaultBlocks(uint64_t bytes);
