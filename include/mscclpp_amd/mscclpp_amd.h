@@ -338,6 +338,33 @@ int mscclppAmdAllReduceRmsNormLaunch(const mscclppAmdRankView* views, int nviews
 /* Scratch bytes per rank that call needs (two halves of nranks regions of rows * cols / 4 16-byte units,
  * each half rounded up to 256); 0: the call is not carried at any setting. */
 size_t mscclppAmdAllReduceRmsNormScratchRequired(int nranks, size_t rows, size_t cols, int dtype);
+/* The same operation -- the same definition, so the same bits of resOut -- for PREFILL sizes by a two-shot
+ * zero-copy pull (kernels/allreduce_rmsnorm_pull.hip): rank q owns rows [q R, (q + 1) R), R =
+ * ceil(rows / nranks), pulls them from every peer's x (peerInput[k]), reduces, adds and normalises them once,
+ * and every rank then copies the other ranks' finished rows out of peerOutput[q] and, with a residual, out of
+ * peerResOut.  y is bit-identical on all ranks, for every grid and from call to call; it need not equal the LL
+ * entry point's y in the last bit (the row's sum of squares is taken in this kernel's lane order).  Views as
+ * for mscclppAmdPullReduceLaunch with MSCCLPP_AMD_PULL_ALLREDUCE (input, output, tokens, peerTokens, expected,
+ * err, peerInput[q], peerOutput[q]; no scratch, no flags).  residual / resOut / gamma: as above.  peerResOut:
+ * NULL without a residual; with one, a host array of nviews x MSCCLPP_AMD_MAX_RANKS entries, [i *
+ * MSCCLPP_AMD_MAX_RANKS + q] = rank q's resOut as view i has it mapped.  In place is carried as output ==
+ * input and resOut[i] == residual[i].  nblocks <= 0: 32 KiB of a rank's rows per workgroup, 8 .. 32 and at most
+ * R, a function of (nranks, rows, cols) alone; every rank must launch the same nblocks.  nthreads <= 0: 256 lanes, 512 when cols > 8192; a lane owns
+ * at most 4 units of 8 elements of a row, so cols <= 32 * nthreads.  There is no byte cap.
+ * 4 (nothing is launched, no device is touched): null views / x / y / gamma / fields, nranks outside 2..8, rows
+ * of 0, cols of 0 or no multiple of 8 or above 32 * nthreads, another dtype, a pointer that is not 16-byte
+ * aligned, resOut without residual or the reverse, a residual without peerResOut, buffers that overlap
+ * otherwise than by the two in-place forms, a bad launch shape or nblocks > MSCCLPP_AMD_MAX_CHANNELS; 5: a
+ * workgroup's rows exceed 4 GiB (more workgroups carry them), or the grid cannot be resident at once. */
+int mscclppAmdAllReduceRmsNormPullLaunch(const mscclppAmdRankView* views, int nviews, int nranks,
+                                         const void* const* residual, void* const* resOut, void* const* peerResOut,
+                                         const void* const* gamma, size_t rows, size_t cols, int dtype, float eps,
+                                         int nblocks, int nthreads, uint64_t budgetTicks, void* stream);
+/* That entry point's answer for the buffers and the shape alone (views: input and output are the only fields
+ * read), host only: 0, 4 or 5 as above, without the views' plumbing, peerResOut and the residency of the grid. */
+int mscclppAmdAllReduceRmsNormPullCheck(const mscclppAmdRankView* views, int nviews, int nranks,
+                                        const void* const* residual, void* const* resOut, const void* const* gamma,
+                                        size_t rows, size_t cols, int dtype, int nblocks, int nthreads);
 /* Send / Recv by a zero-copy pull (kernels/sendrecv.hip): one launch runs a table of point-to-point
  * operations, in table order.  An operation moves `bytes` from `send` on rank `src` to `recv` on
  * rank `dst`: the receiver reads `send` -- the address at which the view of rank `dst` has the
@@ -393,7 +420,7 @@ int mscclppAmdTunedConfigSource(const char* collective, int nranks, size_t bytes
 // 3 reduce + all-gather stores issued, 4 end; zero-copy: 0 start, 1 entry handshake done, 2 reduce +
 // all-gather stores issued, 3 end; LL16: 0 start, 1 step 1 (puts), 2 step 2 (reduce + broadcast),
 // 3 step 3 (unpack) done; LL8: 0 start, 1 puts issued, 2 end; AllToAll: 0 start, 1 entry handshake
-// done, 2 segments stored, 3 end; AllToAll LL: 0 start, 1 puts issued, 2 stored; AllReduce+RMSNorm (of a workgroup's last row): 0 start, 1 puts issued, 2 reduced, 3 normalised; Reduce: 0 start, 1 entry handshake done, 2 result stored (root),
+// done, 2 segments stored, 3 end; AllToAll LL: 0 start, 1 puts issued, 2 stored; AllReduce+RMSNorm (of a workgroup's last row): 0 start, 1 puts issued, 2 reduced, 3 normalised; AllReduce+RMSNorm pull: 0 start, 1 entry handshake done, 2 own rows normalised, 3 peers' rows gathered, 4 end; Reduce: 0 start, 1 entry handshake done, 2 result stored (root),
 // 3 end; Send/Recv: 0 start, 1 readies posted, 2 receives stored, 3 dones seen; pull-reduce (MAX /
 // AVG): 0 start, 1 entry handshake done, 2 own range reduced, 3 peers' slices gathered (AllReduce
 // only), 4 end.  buf = NULL turns it off.  Returns 0,
@@ -415,6 +442,14 @@ int mscclppAmdCommAllReduceAccum(ncclComm_t comm, const void* sendbuff, void* re
  * stream capture when the scratch would have to grow. */
 int mscclppAmdCommAllReduceRmsNorm(ncclComm_t comm, const void* x, void* y, const void* residual, void* resOut,
                                    const void* gamma, size_t rows, size_t cols, int ncclDtype, float eps, void* stream);
+/* The fused AllReduce + residual add + RMSNorm of mscclppAmdAllReduceRmsNormPullLaunch on this communicator:
+ * the same arguments as mscclppAmdCommAllReduceRmsNorm, any size.  x and y (and resOut) are registered like
+ * the buffers of a MAX / AVG AllReduce: collective on first use, cached per allocation, pinned under stream
+ * capture; the arguments are checked first, so a refused call registers nothing.  Every rank must make the
+ * same call.  Refusals as for the launch entry point; also ncclInvalidArgument on a one-rank communicator. */
+int mscclppAmdCommAllReduceRmsNormPull(ncclComm_t comm, const void* x, void* y, const void* residual, void* resOut,
+                                       const void* gamma, size_t rows, size_t cols, int ncclDtype, float eps,
+                                       void* stream);
 /* Reduce-type code (MSCCLPP_AMD_*) for an ncclDataType_t and accumulation type (-1 = AUTO), or -1. */
 int mscclppAmdReduceType(int ncclDtype, int accumNcclDtype);
 int mscclppAmdCommBarrier(ncclComm_t comm);

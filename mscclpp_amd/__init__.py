@@ -178,6 +178,12 @@ def lib():
         "mscclppAmdAllReduceRmsNormLaunch": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(vp), ctypes.POINTER(vp),
                                              ctypes.POINTER(vp), sz, sz, i32, ctypes.c_float, i32, i32, u64, vp],
         "mscclppAmdCommAllReduceRmsNorm": [vp, vp, vp, vp, vp, vp, sz, sz, i32, ctypes.c_float, vp],
+        "mscclppAmdAllReduceRmsNormPullLaunch": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                                 ctypes.POINTER(vp), ctypes.POINTER(vp), sz, sz, i32, ctypes.c_float, i32,
+                                                 i32, u64, vp],
+        "mscclppAmdAllReduceRmsNormPullCheck": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                                ctypes.POINTER(vp), sz, sz, i32, i32, i32],
+        "mscclppAmdCommAllReduceRmsNormPull": [vp, vp, vp, vp, vp, vp, sz, sz, i32, ctypes.c_float, vp],
         "mscclppAmdCommAllToAllLLCount": [vp, ctypes.POINTER(ctypes.c_uint64)],
         "mscclppAmdReduceLaunch": [ctypes.POINTER(RankView), i32, i32, sz, i32, i32, i32, i32, i32, u64, vp],
         "ncclReduce": [vp, vp, sz, i32, i32, i32, vp, vp],
@@ -392,6 +398,7 @@ TRACE_PHASES = {
     "pull_reduce_ll": ("put", "reduce"),
     "alltoall_ll": ("put", "receive"),
     "allreduce_rms_norm": ("put", "reduce", "normalise"),
+    "allreduce_rms_norm_pull": ("entry_handshake", "reduce_normalise", "gather", "exit_handshake"),
 }
 
 
@@ -677,6 +684,30 @@ class InProcessRanks:
                                                       nblocks, nthreads, budget_ticks, stream_ptr(stream))
         check(code, "in-process all_reduce_rms_norm")
 
+    def all_reduce_rms_norm_pull(self, xs, ys, gammas, residuals=None, res_outs=None, eps=1e-6, nblocks=0, nthreads=0,
+                                 budget_ticks=500_000_000, stream=None):
+        """all_reduce_rms_norm for prefill sizes by a two-shot zero-copy pull (mscclppAmdAllReduceRmsNormPullLaunch):
+        the same arguments and the same operation -- res_outs bit for bit -- at any size; each rank reduces and
+        normalises its share of the rows once and the ranks copy one another's.  ys are equal on all ranks for
+        every grid; they may differ from all_reduce_rms_norm's in the last bit."""
+        for r in range(self.n):
+            _rms_norm_tensors(xs[r], ys[r], residuals and residuals[r], res_outs and res_outs[r], gammas[r])
+            if xs[r].shape != xs[0].shape or xs[r].dtype != xs[0].dtype:
+                raise MscclppError(4, "all_reduce_rms_norm_pull: the ranks' tensors differ in shape or dtype")
+        rows, cols = xs[0].shape
+        ptrs = lambda ts: None if ts is None else (ctypes.c_void_p * self.n)(*[None if t is None else t.data_ptr() for t in ts])
+        peer_ro = None
+        if res_outs is not None:  # every view sees rank q's res_out at its own address
+            peer_ro = (ctypes.c_void_p * (self.n * MAX_RANKS))()
+            for r in range(self.n):
+                for q in range(self.n):
+                    peer_ro[r * MAX_RANKS + q] = None if res_outs[q] is None else res_outs[q].data_ptr()
+        code = lib().mscclppAmdAllReduceRmsNormPullLaunch(self.views(xs, ys), self.n, self.n, ptrs(residuals),
+                                                          ptrs(res_outs), peer_ro, ptrs(gammas), rows, cols,
+                                                          DTYPE_CODES.get(xs[0].dtype, -1), eps, nblocks, nthreads,
+                                                          budget_ticks, stream_ptr(stream))
+        check(code, "in-process all_reduce_rms_norm_pull")
+
     def send_recv(self, ops, nblocks=0, nthreads=0, budget_ticks=500_000_000, stream=None):
         """ncclSend / ncclRecv (a whole group) for in-process ranks, one launch.  ops: (src, dst, send,
         recv) in table order -- `send` on rank src (a tensor, read in place by rank dst) lands in
@@ -785,6 +816,21 @@ class Communicator:
         check(lib().mscclppAmdCommAllReduceRmsNorm(self.comm, ptr(x), ptr(y), ptr(residual), ptr(res_out), ptr(gamma),
                                                    rows, cols, NCCL_DTYPES.get(x.dtype, -1), eps, stream_ptr(stream)),
               "mscclppAmdCommAllReduceRmsNorm")
+        return y, res_out
+
+    def all_reduce_rms_norm_pull(self, x, gamma, y=None, residual=None, res_out=None, eps=1e-6, stream=None):
+        """all_reduce_rms_norm for prefill sizes (mscclppAmdCommAllReduceRmsNormPull): the same arguments, defaults
+        and operation at any size, by a two-shot zero-copy pull.  x, y and res_out are registered on first use
+        (collective), like the buffers of a MAX / AVG all_reduce.  Returns (y, res_out)."""
+        y = x if y is None else y
+        if residual is not None and res_out is None:
+            res_out = residual
+        _rms_norm_tensors(x, y, residual, res_out, gamma)
+        rows, cols = x.shape
+        ptr = lambda t: ctypes.c_void_p(None if t is None else t.data_ptr())
+        check(lib().mscclppAmdCommAllReduceRmsNormPull(self.comm, ptr(x), ptr(y), ptr(residual), ptr(res_out), ptr(gamma),
+                                                       rows, cols, NCCL_DTYPES.get(x.dtype, -1), eps, stream_ptr(stream)),
+              "mscclppAmdCommAllReduceRmsNormPull")
         return y, res_out
 
     def reduce_scatter(self, send, recv, op="sum", stream=None):

@@ -291,6 +291,33 @@ int ncclComm::allReduceRmsNorm(const void* x, void* y, const void* residual, voi
   return rc;
 }
 
+int ncclComm::allReduceRmsNormPull(const void* x, void* y, const void* residual, void* resOut, const void* gamma,
+                                   size_t rows, size_t cols, int dtype, float eps, hipStream_t stream) {
+  std::lock_guard<std::mutex> lk(mu);
+  mscclppAmdRankView v = baseView(x, y);
+  const void* const* res = residual || resOut ? &residual : nullptr;
+  void* const* ro = residual || resOut ? &resOut : nullptr;
+  // A call with a bad argument is refused before anything is registered and before any device call; the
+  // answer depends on the arguments alone, so every rank refuses alike.
+  int nblocks = 0, nthreads = 0;
+  if (const int rc = allReduceRmsNormPullCheck(&v, 1, nranks, res, ro, &gamma, rows, cols, dtype, nblocks, nthreads,
+                                               nullptr, nullptr))
+    return rc;
+  v = pullView(x, y, stream);  // the peers read x ...
+  if (y == x) {                // ... and this rank's finished rows out of y (in place: the same registration)
+    for (int r = 0; r < nranks; ++r) v.peerOutput[r] = const_cast<void*>(v.peerInput[r]);
+  } else {
+    const auto outs = registerOutput(y, stream);
+    for (int r = 0; r < nranks; ++r) v.peerOutput[r] = outs[r];
+  }
+  std::array<void*, MSCCLPP_AMD_MAX_RANKS> peerResOut{};
+  if (residual) peerResOut = registerOutput(resOut, stream);
+  const int rc = launchAllReduceRmsNormPull(&v, 1, nranks, res, ro, residual ? peerResOut.data() : nullptr, &gamma, rows,
+                                            cols, dtype, eps, 0, 0, spinBudgetTicks(), stream);
+  mappings.recordUses(stream, device);
+  return rc;
+}
+
 ncclRedOp_t ncclComm::preMulCreate(const PreMulOp& e) {
   std::lock_guard<std::mutex> lk(mu);
   size_t slot = 0;

@@ -498,6 +498,13 @@ struct ncclComm {
   // is refused.  dtype: MSCCLPP_AMD_F16 / _BF16.
   int allReduceRmsNorm(const void* x, void* y, const void* residual, void* resOut, const void* gamma, size_t rows,
                        size_t cols, int dtype, float eps, hipStream_t stream);
+  // The same operation for prefill sizes by a two-shot zero-copy pull (kernels/allreduce_rmsnorm_pull.hip;
+  // DESIGN.md §17j), the pattern of pullReduce's AllReduce: x is what the peers reduce from, y and resOut what
+  // they copy this rank's finished rows from, so all three are registered (y == x: one registration; the
+  // residual itself is never read by a peer).  The arguments are checked first; a refused call registers
+  // nothing.
+  int allReduceRmsNormPull(const void* x, void* y, const void* residual, void* resOut, const void* gamma, size_t rows,
+                           size_t cols, int dtype, float eps, hipStream_t stream);
   ncclRedOp_t preMulCreate(const PreMulOp& e);
   // The live entry of `op` (a copy: the caller launches after the lock is dropped, and the handle may
   // be destroyed as soon as the collective call has returned), or false.

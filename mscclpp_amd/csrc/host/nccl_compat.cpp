@@ -865,6 +865,48 @@ int mscclppAmdCommAllReduceRmsNorm(ncclComm_t comm, const void* x, void* y, cons
   });
 }
 
+// The same operation for prefill sizes by a two-shot zero-copy pull (kernels/allreduce_rmsnorm_pull.hip;
+// DESIGN.md §17j): the views' plumbing is checked here, the buffers, the shape and peerResOut by
+// launchAllReduceRmsNormPull, all before a device is touched; a refusal launches nothing.
+int mscclppAmdAllReduceRmsNormPullLaunch(const mscclppAmdRankView* views, int nviews, int nranks,
+                                         const void* const* residual, void* const* resOut, void* const* peerResOut,
+                                         const void* const* gamma, size_t rows, size_t cols, int dtype, float eps,
+                                         int nblocks, int nthreads, uint64_t budgetTicks, void* stream) {
+  return guarded([&] {
+    ViewNeeds needs;
+    needs.all = kViewInput | kViewOutput | kViewHandshake | kViewPeerInput | kViewPeerOutput;
+    if (!gamma || !viewsValid(views, nviews, nranks, needs)) return (int)ncclInvalidArgument;
+    unsigned seen = 0;
+    for (int i = 0; i < nviews; ++i) {  // no rank twice
+      if ((seen >> views[i].rank) & 1u) return (int)ncclInvalidArgument;
+      seen |= 1u << views[i].rank;
+    }
+    return mscclpp_amd::launchAllReduceRmsNormPull(views, nviews, nranks, residual, resOut, peerResOut, gamma, rows, cols,
+                                                   dtype, eps, nblocks, nthreads,
+                                                   budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream);
+  });
+}
+
+int mscclppAmdAllReduceRmsNormPullCheck(const mscclppAmdRankView* views, int nviews, int nranks,
+                                        const void* const* residual, void* const* resOut, const void* const* gamma,
+                                        size_t rows, size_t cols, int dtype, int nblocks, int nthreads) {
+  return guarded([&] {
+    return mscclpp_amd::allReduceRmsNormPullCheck(views, nviews, nranks, residual, resOut, gamma, rows, cols, dtype,
+                                                  nblocks, nthreads, nullptr, nullptr);
+  });
+}
+
+int mscclppAmdCommAllReduceRmsNormPull(ncclComm_t comm, const void* x, void* y, const void* residual, void* resOut,
+                                       const void* gamma, size_t rows, size_t cols, int ncclDtype, float eps,
+                                       void* stream) {
+  return guarded([&] {
+    if (!comm || comm->nranks < 2) return (int)ncclInvalidArgument;  // (one rank: refused, as §17i)
+    const int dt = ncclDtype == (int)ncclFloat16 ? MSCCLPP_AMD_F16 : ncclDtype == (int)ncclBfloat16 ? MSCCLPP_AMD_BF16 : -1;
+    if (dt < 0) return (int)ncclInvalidArgument;
+    return comm->allReduceRmsNormPull(x, y, residual, resOut, gamma, rows, cols, dt, eps, (hipStream_t)stream);
+  });
+}
+
 int mscclppAmdCommAllToAllLLCount(ncclComm_t comm, uint64_t* count) {
   if (!comm || !count) return ncclInvalidArgument;
   std::lock_guard<std::mutex> lk(comm->mu);

@@ -1,0 +1,77 @@
+// What the two fused AllReduce + residual add + RMSNorm kernels share (allreduce_rmsnorm_ll.hip,
+// allreduce_rmsnorm_pull.hip): the element decode / encode of the definition and the host's
+// check of a call's buffers.
+#pragma once
+
+#include "common.hpp"
+#include "mscclpp_amd/pull_reduce_device.hpp"
+
+namespace mscclpp_amd {
+
+// A buffer resource over exactly `bytes` bytes at p: an offset outside it loads zeros and stores nothing.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t arnorm_rsrc(const void* p, uint32_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
+}
+
+template <int DT>
+__device__ __forceinline__ float arnorm_lo(uint32_t w) {
+  if constexpr (DT == kF16) return f16_to_f32(w & 0xffffu);
+  else return bf16_lo(w);
+}
+template <int DT>
+__device__ __forceinline__ float arnorm_hi(uint32_t w) {
+  if constexpr (DT == kF16) return f16_to_f32(w >> 16);
+  else return bf16_hi(w);
+}
+// Two fp32 values, each rounded once (RNE) to DT and packed {lo, hi}.  The arguments are values of their
+// own (fp32_value / fp32_product), so no conversion is selected together with the operation before it.
+template <int DT>
+__device__ __forceinline__ uint32_t arnorm_pack(float lo, float hi) {
+  if constexpr (DT == kF16) {
+    const _Float16 l = (_Float16)lo, h = (_Float16)hi;
+    return (uint32_t)__builtin_bit_cast(uint16_t, l) | ((uint32_t)__builtin_bit_cast(uint16_t, h) << 16);
+  } else {
+    const __bf16 l = (__bf16)lo, h = (__bf16)hi;
+    return (uint32_t)__builtin_bit_cast(uint16_t, l) | ((uint32_t)__builtin_bit_cast(uint16_t, h) << 16);
+  }
+}
+
+inline bool arNormOverlap(const void* p, size_t pn, const void* q, size_t qn) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return a < b + qn && b < a + pn;
+}
+
+// The buffers of a call, host only: x, y and gamma present on every view, a residual with its output on every
+// view or on none, every pointer aligned to `align` bytes, and no overlap but y == x and resOut == residual --
+// inside a view between any two buffers, between views wherever one of the two is written (replicated
+// read-only buffers may be shared).  bytes: of one [rows][cols] buffer.
+inline bool arNormBuffersOk(const mscclppAmdRankView* views, int nviews, const void* const* residual,
+                            void* const* resOut, const void* const* gamma, uint64_t bytes, size_t cols, unsigned align) {
+  struct Buf { const void* p; size_t n; bool written; int view; };
+  Buf all[kMaxRanks * 5];
+  int nb = 0;
+  const bool withRes = residual && residual[0];
+  for (int i = 0; i < nviews; ++i) {
+    const void* x = views[i].input;
+    const void* y = views[i].output;
+    const void* r = residual ? residual[i] : nullptr;
+    const void* ro = resOut ? resOut[i] : nullptr;
+    if (!x || !y || !gamma[i] || (r != nullptr) != withRes || (ro != nullptr) != withRes) return false;
+    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)r | (uintptr_t)ro | (uintptr_t)gamma[i]) % align) return false;
+    all[nb++] = Buf{x, bytes, y == x, i};
+    if (y != x) all[nb++] = Buf{y, bytes, true, i};
+    all[nb++] = Buf{gamma[i], cols * 2, false, i};
+    if (withRes) {
+      all[nb++] = Buf{r, bytes, ro == r, i};
+      if (ro != r) all[nb++] = Buf{ro, bytes, true, i};
+    }
+  }
+  for (int b = 0; b < nb; ++b)
+    for (int c = 0; c < b; ++c)
+      if ((all[b].view == all[c].view || all[b].written || all[c].written) &&
+          arNormOverlap(all[b].p, all[b].n, all[c].p, all[c].n))
+        return false;
+  return true;
+}
+
+}  // namespace mscclpp_amd

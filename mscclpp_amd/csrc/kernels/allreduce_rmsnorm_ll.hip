@@ -30,9 +30,9 @@
 //    reuse by the argument of pull_reduce_ll.hip: rows >= 1, so every rank polls a packet of every other
 //    rank in every call.  The scratch and the flags are the communicator's, shared with the other LL kernels.
 //    Trace stamps (of the workgroup's last row): 0 start, 1 puts issued, 2 reduced, 3 normalised.
+#include "allreduce_rmsnorm.hpp"
 #include "launch.hpp"
 #include "ll_units.hpp"
-#include "mscclpp_amd/pull_reduce_device.hpp"
 
 #include <stdlib.h>
 
@@ -98,34 +98,6 @@ struct ArNormArgs {
   int pad;
 };
 static_assert(sizeof(ArNormArgs<kMaxRanks>) <= 4096, "in-process AllReduce+RMSNorm arguments exceed the kernel-argument limit");
-
-// A buffer resource over exactly `bytes` bytes at p: an offset outside it loads zeros and stores nothing.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t arnorm_rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-
-template <int DT>
-__device__ __forceinline__ float arnorm_lo(uint32_t w) {
-  if constexpr (DT == kF16) return f16_to_f32(w & 0xffffu);
-  else return bf16_lo(w);
-}
-template <int DT>
-__device__ __forceinline__ float arnorm_hi(uint32_t w) {
-  if constexpr (DT == kF16) return f16_to_f32(w >> 16);
-  else return bf16_hi(w);
-}
-// Two fp32 values, each rounded once (RNE) to DT and packed {lo, hi}.  The arguments are values of their
-// own (fp32_value / fp32_product), so no conversion is selected together with the operation before it.
-template <int DT>
-__device__ __forceinline__ uint32_t arnorm_pack(float lo, float hi) {
-  if constexpr (DT == kF16) {
-    const _Float16 l = (_Float16)lo, h = (_Float16)hi;
-    return (uint32_t)__builtin_bit_cast(uint16_t, l) | ((uint32_t)__builtin_bit_cast(uint16_t, h) << 16);
-  } else {
-    const __bf16 l = (__bf16)lo, h = (__bf16)hi;
-    return (uint32_t)__builtin_bit_cast(uint16_t, l) | ((uint32_t)__builtin_bit_cast(uint16_t, h) << 16);
-  }
-}
 
 // zq of one word: the fp32 sum over the ranks in rank order (x[p] is rank p's word, `own` at position
 // rank), plus the residual word where there is one, rounded once.
@@ -317,11 +289,6 @@ static int launchArNormDT(int upl, const mscclppAmdRankView* views, int nviews, 
   }
 }
 
-static bool arNormOverlap(const void* p, size_t pn, const void* q, size_t qn) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + qn && b < a + pn;
-}
-
 // The checks of a call's arguments, host only: 0, 4 (invalid) or 5 (a size the path does not carry); the
 // views' input / output are the only fields read.  nthreads comes back as the lanes the launch takes, *upl
 // as its units per lane.  The communicator asks this before it touches its own bookkeeping.
@@ -339,32 +306,8 @@ int allReduceRmsNormCheck(const mscclppAmdRankView* views, int nviews, int nrank
   if (upl) *upl = perLane <= 1 ? 1 : perLane <= 2 ? 2 : perLane <= 4 ? 4 : 8;
   const uint64_t bytes = (rows > (1ull << 32) ? (1ull << 32) : (uint64_t)rows) * cols * 2;  // (no overflow: cols is bounded)
   // pointers: present, 8-byte aligned, a residual with its output on every view or on none, and no overlap
-  // but y == x and resOut == residual: inside a view between any two buffers, between views wherever one
-  // of the two is written (replicated read-only buffers may be shared)
-  struct Buf { const void* p; size_t n; bool written; int view; };
-  Buf all[kMaxRanks * 5];
-  int nb = 0;
-  const bool withRes = residual && residual[0];
-  for (int i = 0; i < nviews; ++i) {
-    const void* x = views[i].input;
-    const void* y = views[i].output;
-    const void* r = residual ? residual[i] : nullptr;
-    const void* ro = resOut ? resOut[i] : nullptr;
-    if (!x || !y || !gamma[i] || (r != nullptr) != withRes || (ro != nullptr) != withRes) return 4;
-    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)r | (uintptr_t)ro | (uintptr_t)gamma[i]) % 8) return 4;
-    all[nb++] = Buf{x, bytes, y == x, i};
-    if (y != x) all[nb++] = Buf{y, bytes, true, i};
-    all[nb++] = Buf{gamma[i], cols * 2, false, i};
-    if (withRes) {
-      all[nb++] = Buf{r, bytes, ro == r, i};
-      if (ro != r) all[nb++] = Buf{ro, bytes, true, i};
-    }
-  }
-  for (int b = 0; b < nb; ++b)
-    for (int c = 0; c < b; ++c)
-      if ((all[b].view == all[c].view || all[b].written || all[c].written) &&
-          arNormOverlap(all[b].p, all[b].n, all[c].p, all[c].n))
-        return 4;
+  // but y == x and resOut == residual
+  if (!arNormBuffersOk(views, nviews, residual, resOut, gamma, bytes, cols, 8)) return 4;
   ArNormGeom g;
   return bytes > arNormMaxBytes() || !arNormGeometry(nranks, rows, cols, dtype, &g) ? 5 : 0;
 }
