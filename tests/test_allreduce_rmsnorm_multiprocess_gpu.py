@@ -1,6 +1,7 @@
 """Communicator.all_reduce_rms_norm with one rank per process: the judges of test_allreduce_rmsnorm_gpu.py on
 (3, 252) and (2, 8192), a captured call replayed on new data, the refusals alike on every rank with a good
-call behind them, no device error.  Not tested: a captured call whose scratch would have to grow (64 MiB are
+call behind them, no device error; at 3 processes one call on `order_inputs` (fp32 adds that round, so "the own term
+at position rank" is visible per process).  Not tested: a captured call whose scratch would have to grow (64 MiB are
 held from init and the largest call carried needs 32 MiB, so no call reaches that refusal through the ABI)."""
 import multiprocessing as mp
 import os
@@ -15,9 +16,9 @@ import allreduce_rmsnorm_model as M
 pytestmark = pytest.mark.gpu
 
 
-def call(torch, comm, rank, n, dt, rows, cols, mode, seed, graph=None):
+def call(torch, comm, rank, n, dt, rows, cols, mode, seed, graph=None, make=M.inputs):
     """A call on fresh inputs, or a replay of graph = (graph, x, residual, y, res_out, gamma): (failed checks, y)."""
-    xs, res, gamma = M.inputs(seed, n, rows, cols, dt, mode != "none")
+    xs, res, gamma = make(seed, n, rows, cols, dt, mode != "none")
     if graph:
         g, x, r_in, y, r_out, gam = graph
         for buf, bits in ((x, xs[rank]), (r_in, res), (gam, gamma)):
@@ -72,6 +73,8 @@ def worker(rank, n, uid, q):
                 for mode in ("none", "out_of_place", "in_place"):
                     seed += 1
                     res[f"{dt} {rows}x{cols} {mode}"] = call(torch, comm, rank, n, dt, rows, cols, mode, seed)
+        if n == 3:  # adds that round: a process that summed its own term first would show here
+            res["order_inputs"] = call(torch, comm, rank, n, "bf16", 6, 2056, "out_of_place", 160, make=M.order_inputs)
         rows, cols, dt = 3, 252, "bf16"  # a capture behind an eager call of the same shape, replayed on new data
         res["eager before the capture"] = call(torch, comm, rank, n, dt, rows, cols, "out_of_place", 200)
         bufs = [M.Guarded(torch, rows, cols, dt) for _ in range(4)] + [M.Guarded(torch, 1, cols, dt)]

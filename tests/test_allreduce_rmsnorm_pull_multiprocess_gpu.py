@@ -1,7 +1,8 @@
 """Communicator.all_reduce_rms_norm_pull with one rank per process: the judges of test_allreduce_rmsnorm_pull_gpu.py
 on (3, 248) and (2, 16384), one call of 65 x 8192 (which the LL entry point refuses for its size), an eager call
 whose buffers are then captured and replayed on new data, the refusals alike on every rank with a good call behind
-them, no device error, y equal across the ranks."""
+them, no device error, y equal across the ranks; at 3 processes one call on `order_inputs` (fp32 adds that round, so
+"the own term at position rank" is visible per process)."""
 import multiprocessing as mp
 import os
 import traceback
@@ -22,9 +23,9 @@ def buffers(torch, rows, cols, dt, mode):  # x, residual, y, res_out, gamma
             r_in if mode != "out_of_place" else M.Guarded(torch, rows, cols, dt), M.Guarded(torch, 1, cols, dt))
 
 
-def call(torch, comm, rank, n, dt, rows, cols, mode, seed, bufs=None, graph=None):
+def call(torch, comm, rank, n, dt, rows, cols, mode, seed, bufs=None, graph=None, make=M.inputs):
     """A call on fresh inputs (in `bufs`, or in new buffers), or a replay of `graph` over bufs: (failed checks, y)."""
-    xs, res, gamma = M.inputs(seed, n, rows, cols, dt, mode != "none")
+    xs, res, gamma = make(seed, n, rows, cols, dt, mode != "none")
     x, r_in, y, r_out, gam = bufs or buffers(torch, rows, cols, dt, mode)
     for buf, bits in ((x, xs[rank]), (r_in, res), (gam, gamma)):
         if buf is not None:
@@ -75,6 +76,8 @@ def worker(rank, n, uid, q):
                     seed += 1
                     res[f"{dt} {rows}x{cols} {mode}"] = call(torch, comm, rank, n, dt, rows, cols, mode, seed)
         res["65x8192"] = call(torch, comm, rank, n, "bf16", 65, 8192, "out_of_place", 150)
+        if n == 3:  # adds that round: a process that summed its own term first would show here
+            res["order_inputs"] = call(torch, comm, rank, n, "bf16", 6, 2056, "out_of_place", 160, make=M.order_inputs)
         rows, cols, dt = 3, 248, "bf16"  # an eager call, then the same buffers captured and replayed on new data
         bufs = buffers(torch, rows, cols, dt, "out_of_place")
         res["eager before the capture"] = call(torch, comm, rank, n, dt, rows, cols, "out_of_place", 200, bufs)
