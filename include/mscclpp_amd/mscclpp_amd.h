@@ -365,6 +365,33 @@ int mscclppAmdAllReduceRmsNormPullLaunch(const mscclppAmdRankView* views, int nv
 int mscclppAmdAllReduceRmsNormPullCheck(const mscclppAmdRankView* views, int nviews, int nranks,
                                         const void* const* residual, void* const* resOut, const void* const* gamma,
                                         size_t rows, size_t cols, int dtype, int nblocks, int nthreads);
+/* That pull with the normalised rows quantised for an FP8 linear layer (kernels/allreduce_rmsnorm_quant_pull.hip;
+ * DESIGN.md §17k): resOut as above, bit for bit; y -- the pull entry point's y at the same (cols, nthreads),
+ * bit for bit -- is not stored but leaves as
+ *   amax = max_j |y_j|, scale[row] = max(amax / 448, 2^-126) (fp32), q[row][j] = e4m3(clamp(y_j * (1 / scale), +-448))
+ * with both divisions correctly rounded, one fp32 product per element and one rounding to nearest even into OCP
+ * FP8 e4m3: q (view.output) is [rows][cols] BYTES, scale[i] [rows] floats.  q and scale are bit-identical on all
+ * ranks, for every grid and from call to call.  An all-zero row gives scale = 2^-126 and q = +-0; a row whose y
+ * holds a NaN or an infinity has an unspecified q and scale (its resOut and its neighbours are as defined, and
+ * nothing faults).  Views, residual / resOut / peerResOut / gamma, nblocks and nthreads as for
+ * mscclppAmdAllReduceRmsNormPullLaunch, with peerOutput[q] = rank q's q.  scale: a host array with one entry per
+ * view; peerScale: nviews x MSCCLPP_AMD_MAX_RANKS entries, [i * MSCCLPP_AMD_MAX_RANKS + q] = rank q's scale as
+ * view i has it mapped.  resOut[i] == residual[i] is the only in-place form.
+ * 4: as that entry point, and cols no multiple of 16, a null q or scale, a q that is not 16-byte or a scale that
+ * is not 4-byte aligned, a q (rows * cols bytes) or a scale (rows * 4 bytes) that overlaps any buffer of any
+ * view, or no peerScale; 5: as that entry point (the limit applies to a workgroup's rows of x). */
+int mscclppAmdAllReduceRmsNormQuantPullLaunch(const mscclppAmdRankView* views, int nviews, int nranks,
+                                              const void* const* residual, void* const* resOut,
+                                              void* const* peerResOut, const void* const* gamma, void* const* scale,
+                                              void* const* peerScale, size_t rows, size_t cols, int dtype, float eps,
+                                              int nblocks, int nthreads, uint64_t budgetTicks, void* stream);
+/* That entry point's answer for the buffers and the shape alone (views: input and output are the only fields
+ * read), host only: 0, 4 or 5 as above, without the views' plumbing, peerResOut, peerScale and the residency of
+ * the grid. */
+int mscclppAmdAllReduceRmsNormQuantPullCheck(const mscclppAmdRankView* views, int nviews, int nranks,
+                                             const void* const* residual, void* const* resOut,
+                                             const void* const* gamma, void* const* scale, size_t rows, size_t cols,
+                                             int dtype, int nblocks, int nthreads);
 /* Send / Recv by a zero-copy pull (kernels/sendrecv.hip): one launch runs a table of point-to-point
  * operations, in table order.  An operation moves `bytes` from `send` on rank `src` to `recv` on
  * rank `dst`: the receiver reads `send` -- the address at which the view of rank `dst` has the
@@ -420,7 +447,7 @@ int mscclppAmdTunedConfigSource(const char* collective, int nranks, size_t bytes
 // 3 reduce + all-gather stores issued, 4 end; zero-copy: 0 start, 1 entry handshake done, 2 reduce +
 // all-gather stores issued, 3 end; LL16: 0 start, 1 step 1 (puts), 2 step 2 (reduce + broadcast),
 // 3 step 3 (unpack) done; LL8: 0 start, 1 puts issued, 2 end; AllToAll: 0 start, 1 entry handshake
-// done, 2 segments stored, 3 end; AllToAll LL: 0 start, 1 puts issued, 2 stored; AllReduce+RMSNorm (of a workgroup's last row): 0 start, 1 puts issued, 2 reduced, 3 normalised; AllReduce+RMSNorm pull: 0 start, 1 entry handshake done, 2 own rows normalised, 3 peers' rows gathered, 4 end; Reduce: 0 start, 1 entry handshake done, 2 result stored (root),
+// done, 2 segments stored, 3 end; AllToAll LL: 0 start, 1 puts issued, 2 stored; AllReduce+RMSNorm (of a workgroup's last row): 0 start, 1 puts issued, 2 reduced, 3 normalised; AllReduce+RMSNorm pull: 0 start, 1 entry handshake done, 2 own rows normalised, 3 peers' rows gathered, 4 end (its quantising form: the same five); Reduce: 0 start, 1 entry handshake done, 2 result stored (root),
 // 3 end; Send/Recv: 0 start, 1 readies posted, 2 receives stored, 3 dones seen; pull-reduce (MAX /
 // AVG): 0 start, 1 entry handshake done, 2 own range reduced, 3 peers' slices gathered (AllReduce
 // only), 4 end.  buf = NULL turns it off.  Returns 0,
@@ -450,6 +477,14 @@ int mscclppAmdCommAllReduceRmsNorm(ncclComm_t comm, const void* x, void* y, cons
 int mscclppAmdCommAllReduceRmsNormPull(ncclComm_t comm, const void* x, void* y, const void* residual, void* resOut,
                                        const void* gamma, size_t rows, size_t cols, int ncclDtype, float eps,
                                        void* stream);
+/* The quantising form, mscclppAmdAllReduceRmsNormQuantPullLaunch, on this communicator: q is [rows][cols] e4m3
+ * bytes, scale [rows] floats; x, q, scale and resOut are registered as above (collective on first use, cached
+ * per allocation, pinned under stream capture), after the arguments are checked.  resOut == residual is the only
+ * in-place form.  Every rank must make the same call.  Refusals as for the launch entry point; also
+ * ncclInvalidArgument on a one-rank communicator. */
+int mscclppAmdCommAllReduceRmsNormQuantPull(ncclComm_t comm, const void* x, void* q, float* scale, const void* residual,
+                                            void* resOut, const void* gamma, size_t rows, size_t cols, int ncclDtype,
+                                            float eps, void* stream);
 /* Reduce-type code (MSCCLPP_AMD_*) for an ncclDataType_t and accumulation type (-1 = AUTO), or -1. */
 int mscclppAmdReduceType(int ncclDtype, int accumNcclDtype);
 int mscclppAmdCommBarrier(ncclComm_t comm);

@@ -184,6 +184,14 @@ def lib():
         "mscclppAmdAllReduceRmsNormPullCheck": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(vp), ctypes.POINTER(vp),
                                                 ctypes.POINTER(vp), sz, sz, i32, i32, i32],
         "mscclppAmdCommAllReduceRmsNormPull": [vp, vp, vp, vp, vp, vp, sz, sz, i32, ctypes.c_float, vp],
+        "mscclppAmdAllReduceRmsNormQuantPullLaunch": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(vp),
+                                                      ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                                      ctypes.POINTER(vp), ctypes.POINTER(vp), sz, sz, i32, ctypes.c_float,
+                                                      i32, i32, u64, vp],
+        "mscclppAmdAllReduceRmsNormQuantPullCheck": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(vp),
+                                                     ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), sz, sz,
+                                                     i32, i32, i32],
+        "mscclppAmdCommAllReduceRmsNormQuantPull": [vp, vp, vp, vp, vp, vp, vp, sz, sz, i32, ctypes.c_float, vp],
         "mscclppAmdCommAllToAllLLCount": [vp, ctypes.POINTER(ctypes.c_uint64)],
         "mscclppAmdReduceLaunch": [ctypes.POINTER(RankView), i32, i32, sz, i32, i32, i32, i32, i32, u64, vp],
         "ncclReduce": [vp, vp, sz, i32, i32, i32, vp, vp],
@@ -399,6 +407,7 @@ TRACE_PHASES = {
     "alltoall_ll": ("put", "receive"),
     "allreduce_rms_norm": ("put", "reduce", "normalise"),
     "allreduce_rms_norm_pull": ("entry_handshake", "reduce_normalise", "gather", "exit_handshake"),
+    "allreduce_rms_norm_quant_pull": ("entry_handshake", "reduce_normalise_quantise", "gather", "exit_handshake"),
 }
 
 
@@ -485,6 +494,17 @@ def _rms_norm_tensors(x, y, residual, res_out, gamma):
         ok = ok and (t is None or (t.dtype == x.dtype and t.is_contiguous() and (t is gamma or t.shape == x.shape)))
     if not ok:
         raise MscclppError(4, "all_reduce_rms_norm: tensors of one dtype, contiguous, x's shape, gamma of its columns")
+
+
+def _rms_norm_quant_tensors(x, q, scale, residual, res_out, gamma):
+    """_rms_norm_tensors for the quantising entry points: q is float8_e4m3fn or uint8 of x's shape, scale float32 of
+    its rows, both contiguous."""
+    _rms_norm_tensors(x, x, residual, res_out, gamma)
+    ok = q is not None and q.dtype in (torch.float8_e4m3fn, torch.uint8) and q.shape == x.shape and q.is_contiguous()
+    ok = ok and scale is not None and scale.dtype == torch.float32 and tuple(scale.shape) == (x.shape[0],)
+    if not (ok and scale.is_contiguous()):
+        raise MscclppError(4, "all_reduce_rms_norm_quant_pull: q of float8_e4m3fn / uint8 and x's shape, scale of "
+                              "float32 and [rows], both contiguous")
 
 
 def all_reduce_rms_norm_scratch_required(nranks, rows, cols, dtype_code):
@@ -708,6 +728,30 @@ class InProcessRanks:
                                                           budget_ticks, stream_ptr(stream))
         check(code, "in-process all_reduce_rms_norm_pull")
 
+    def all_reduce_rms_norm_quant_pull(self, xs, qs, scales, gammas, residuals=None, res_outs=None, eps=1e-6, nblocks=0,
+                                       nthreads=0, budget_ticks=500_000_000, stream=None):
+        """all_reduce_rms_norm_pull whose normalised rows leave quantised (mscclppAmdAllReduceRmsNormQuantPullLaunch):
+        qs[r] is a float8_e4m3fn (or uint8) tensor of xs[r]'s shape, scales[r] a float32 tensor of its rows; per row
+        scale = max(max|y| / 448, 2^-126) and q = e4m3(y / scale) of that method's y, which is not stored.  res_outs
+        are that method's bits; qs and scales are equal on all ranks for every grid.  cols % 16 == 0; qs and scales
+        overlap nothing, res_outs[r] may be residuals[r]."""
+        for r in range(self.n):
+            _rms_norm_quant_tensors(xs[r], qs[r], scales[r], residuals and residuals[r], res_outs and res_outs[r],
+                                    gammas[r])
+            if xs[r].shape != xs[0].shape or xs[r].dtype != xs[0].dtype:
+                raise MscclppError(4, "all_reduce_rms_norm_quant_pull: the ranks' tensors differ in shape or dtype")
+        rows, cols = xs[0].shape
+        ptrs = lambda ts: None if ts is None else (ctypes.c_void_p * self.n)(*[None if t is None else t.data_ptr() for t in ts])
+        peers = lambda ts: None if ts is None else (ctypes.c_void_p * (self.n * MAX_RANKS))(
+            *[ts[q].data_ptr() if q < self.n and ts[q] is not None else None
+              for _ in range(self.n) for q in range(MAX_RANKS)])  # every view sees rank q's buffer at its own address
+        code = lib().mscclppAmdAllReduceRmsNormQuantPullLaunch(self.views(xs, qs), self.n, self.n, ptrs(residuals),
+                                                               ptrs(res_outs), peers(res_outs), ptrs(gammas),
+                                                               ptrs(scales), peers(scales), rows, cols,
+                                                               DTYPE_CODES.get(xs[0].dtype, -1), eps, nblocks, nthreads,
+                                                               budget_ticks, stream_ptr(stream))
+        check(code, "in-process all_reduce_rms_norm_quant_pull")
+
     def send_recv(self, ops, nblocks=0, nthreads=0, budget_ticks=500_000_000, stream=None):
         """ncclSend / ncclRecv (a whole group) for in-process ranks, one launch.  ops: (src, dst, send,
         recv) in table order -- `send` on rank src (a tensor, read in place by rank dst) lands in
@@ -832,6 +876,28 @@ class Communicator:
                                                        rows, cols, NCCL_DTYPES.get(x.dtype, -1), eps, stream_ptr(stream)),
               "mscclppAmdCommAllReduceRmsNormPull")
         return y, res_out
+
+    def all_reduce_rms_norm_quant_pull(self, x, gamma, q=None, scale=None, residual=None, res_out=None, eps=1e-6,
+                                       stream=None):
+        """all_reduce_rms_norm_pull with its y quantised per row for an FP8 linear layer
+        (mscclppAmdCommAllReduceRmsNormQuantPull): q (float8_e4m3fn or uint8, x's shape; default: a new float8_e4m3fn
+        tensor) = e4m3(y / scale), scale (float32, [rows]; default: new) = max(max|y| / 448, 2^-126) per row.  y is
+        not stored; res_out defaults to the residual.  x.shape[1] % 16 == 0.  x, q, scale and res_out are registered
+        on first use (collective), so pass the same q and scale again where the call repeats.  Returns (q, scale,
+        res_out)."""
+        if x is not None and x.dim() == 2:
+            q = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device) if q is None else q
+            scale = torch.empty(x.shape[0], dtype=torch.float32, device=x.device) if scale is None else scale
+        if residual is not None and res_out is None:
+            res_out = residual
+        _rms_norm_quant_tensors(x, q, scale, residual, res_out, gamma)
+        rows, cols = x.shape
+        ptr = lambda t: ctypes.c_void_p(None if t is None else t.data_ptr())
+        check(lib().mscclppAmdCommAllReduceRmsNormQuantPull(self.comm, ptr(x), ptr(q), ptr(scale), ptr(residual),
+                                                            ptr(res_out), ptr(gamma), rows, cols,
+                                                            NCCL_DTYPES.get(x.dtype, -1), eps, stream_ptr(stream)),
+              "mscclppAmdCommAllReduceRmsNormQuantPull")
+        return q, scale, res_out
 
     def reduce_scatter(self, send, recv, op="sum", stream=None):
         """ncclReduceScatter(send, recv, recvcount, dtype, op, comm, stream)."""

@@ -505,6 +505,11 @@ struct ncclComm {
   // nothing.
   int allReduceRmsNormPull(const void* x, void* y, const void* residual, void* resOut, const void* gamma, size_t rows,
                            size_t cols, int dtype, float eps, hipStream_t stream);
+  // That kernel with y leaving as e4m3 bytes `q` and one fp32 `scale` per row
+  // (kernels/allreduce_rmsnorm_quant_pull.hip): x, q, scale and resOut are registered; q and
+  // scale overlap nothing, so there is no in-place form but resOut == residual.
+  int allReduceRmsNormQuantPull(const void* x, void* q, float* scale, const void* residual, void* resOut,
+                                const void* gamma, size_t rows, size_t cols, int dtype, float eps, hipStream_t stream);
   ncclRedOp_t preMulCreate(const PreMulOp& e);
   // The live entry of `op` (a copy: the caller launches after the lock is dropped, and the handle may
   // be destroyed as soon as the collective call has returned), or false.

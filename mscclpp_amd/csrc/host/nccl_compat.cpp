@@ -907,6 +907,51 @@ int mscclppAmdCommAllReduceRmsNormPull(ncclComm_t comm, const void* x, void* y, 
   });
 }
 
+// The pull kernel with y quantised to e4m3 and one scale per row (kernels/allreduce_rmsnorm_quant_pull.hip;
+// DESIGN.md §17k): the views' plumbing is checked here, the buffers, the shape, peerResOut and peerScale by
+// launchAllReduceRmsNormQuantPull, all before a device is touched; a refusal launches nothing.
+int mscclppAmdAllReduceRmsNormQuantPullLaunch(const mscclppAmdRankView* views, int nviews, int nranks,
+                                              const void* const* residual, void* const* resOut,
+                                              void* const* peerResOut, const void* const* gamma, void* const* scale,
+                                              void* const* peerScale, size_t rows, size_t cols, int dtype, float eps,
+                                              int nblocks, int nthreads, uint64_t budgetTicks, void* stream) {
+  return guarded([&] {
+    ViewNeeds needs;
+    needs.all = kViewInput | kViewOutput | kViewHandshake | kViewPeerInput | kViewPeerOutput;
+    if (!gamma || !viewsValid(views, nviews, nranks, needs)) return (int)ncclInvalidArgument;
+    unsigned seen = 0;
+    for (int i = 0; i < nviews; ++i) {  // no rank twice
+      if ((seen >> views[i].rank) & 1u) return (int)ncclInvalidArgument;
+      seen |= 1u << views[i].rank;
+    }
+    return mscclpp_amd::launchAllReduceRmsNormQuantPull(views, nviews, nranks, residual, resOut, peerResOut, gamma, scale,
+                                                        peerScale, rows, cols, dtype, eps, nblocks, nthreads,
+                                                        budgetTicks ? budgetTicks : spinBudgetTicks(),
+                                                        (hipStream_t)stream);
+  });
+}
+
+int mscclppAmdAllReduceRmsNormQuantPullCheck(const mscclppAmdRankView* views, int nviews, int nranks,
+                                             const void* const* residual, void* const* resOut,
+                                             const void* const* gamma, void* const* scale, size_t rows, size_t cols,
+                                             int dtype, int nblocks, int nthreads) {
+  return guarded([&] {
+    return mscclpp_amd::allReduceRmsNormQuantPullCheck(views, nviews, nranks, residual, resOut, gamma, scale, rows, cols,
+                                                       dtype, nblocks, nthreads, nullptr, nullptr);
+  });
+}
+
+int mscclppAmdCommAllReduceRmsNormQuantPull(ncclComm_t comm, const void* x, void* q, float* scale, const void* residual,
+                                            void* resOut, const void* gamma, size_t rows, size_t cols, int ncclDtype,
+                                            float eps, void* stream) {
+  return guarded([&] {
+    if (!comm || comm->nranks < 2) return (int)ncclInvalidArgument;  // (one rank: refused, as §17i)
+    const int dt = ncclDtype == (int)ncclFloat16 ? MSCCLPP_AMD_F16 : ncclDtype == (int)ncclBfloat16 ? MSCCLPP_AMD_BF16 : -1;
+    if (dt < 0) return (int)ncclInvalidArgument;
+    return comm->allReduceRmsNormQuantPull(x, q, scale, residual, resOut, gamma, rows, cols, dt, eps, (hipStream_t)stream);
+  });
+}
+
 int mscclppAmdCommAllToAllLLCount(ncclComm_t comm, uint64_t* count) {
   if (!comm || !count) return ncclInvalidArgument;
   std::lock_guard<std::mutex> lk(comm->mu);

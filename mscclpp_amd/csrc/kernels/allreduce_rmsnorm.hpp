@@ -1,6 +1,6 @@
-// What the two fused AllReduce + residual add + RMSNorm kernels share (allreduce_rmsnorm_ll.hip,
-// allreduce_rmsnorm_pull.hip): the element decode / encode of the definition and the host's
-// check of a call's buffers.
+// What the fused AllReduce + residual add + RMSNorm kernels share (allreduce_rmsnorm_ll.hip,
+// allreduce_rmsnorm_pull.hip, allreduce_rmsnorm_quant_pull.hip): the element decode / encode of the definition
+// (DESIGN.md §17i), the geometry of the two pull kernels and the host's check of a call's buffers.
 #pragma once
 
 #include "common.hpp"
@@ -35,6 +35,29 @@ __device__ __forceinline__ uint32_t arnorm_pack(float lo, float hi) {
     return (uint32_t)__builtin_bit_cast(uint16_t, l) | ((uint32_t)__builtin_bit_cast(uint16_t, h) << 16);
   }
 }
+
+// The two-shot pull kernels' (allreduce_rmsnorm_pull.hip, allreduce_rmsnorm_quant_pull.hip) one statement of
+// the geometry; the host's checks, the launchers and the kernels use it.
+struct ArNormPullGeom {
+  uint32_t rows;
+  uint32_t upr;    // 16-byte units per row = cols / 8
+  uint32_t slice;  // R: rows per rank
+  uint32_t rpb;    // rows per workgroup inside a slice
+};
+
+// Workgroup b's rows of rank q's slice: [*row0, *row0 + the result).
+__host__ __device__ inline uint32_t arNormPullRows(const ArNormPullGeom& g, uint32_t q, uint32_t b, uint32_t* row0) {
+  const uint64_t lo = (uint64_t)b * g.rpb;
+  uint64_t hi = lo + g.rpb < g.slice ? lo + g.rpb : g.slice;
+  const uint64_t first = (uint64_t)q * g.slice + lo;
+  hi += (uint64_t)q * g.slice;
+  if (hi > g.rows) hi = g.rows;
+  *row0 = (uint32_t)first;
+  return lo < g.slice && first < hi ? (uint32_t)(hi - first) : 0u;
+}
+
+constexpr int kArNormPullMaxUPL = 4;
+constexpr int kArNormPullCopyUnits = 4;  // phase 2: 16-byte loads per lane and buffer in flight
 
 inline bool arNormOverlap(const void* p, size_t pn, const void* q, size_t qn) {
   const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;

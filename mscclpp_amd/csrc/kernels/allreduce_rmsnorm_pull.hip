@@ -46,25 +46,6 @@
 
 namespace mscclpp_amd {
 
-// The one statement of the geometry; the host's check, the launcher and the kernel use it.
-struct ArNormPullGeom {
-  uint32_t rows;
-  uint32_t upr;    // 16-byte units per row = cols / 8
-  uint32_t slice;  // R: rows per rank
-  uint32_t rpb;    // rows per workgroup inside a slice
-};
-
-// Workgroup b's rows of rank q's slice: [*row0, *row0 + the result).
-__host__ __device__ inline uint32_t arNormPullRows(const ArNormPullGeom& g, uint32_t q, uint32_t b, uint32_t* row0) {
-  const uint64_t lo = (uint64_t)b * g.rpb;
-  uint64_t hi = lo + g.rpb < g.slice ? lo + g.rpb : g.slice;
-  const uint64_t first = (uint64_t)q * g.slice + lo;
-  hi += (uint64_t)q * g.slice;
-  if (hi > g.rows) hi = g.rows;
-  *row0 = (uint32_t)first;
-  return lo < g.slice && first < hi ? (uint32_t)(hi - first) : 0u;
-}
-
 template <int NV>
 struct ArNormPullArgs {
   Views<NV> views;
@@ -81,9 +62,6 @@ struct ArNormPullArgs {
   int pad;
 };
 static_assert(sizeof(ArNormPullArgs<kMaxRanks>) <= 4096, "in-process AllReduce+RMSNorm pull arguments exceed the kernel-argument limit");
-
-constexpr int kArNormPullMaxUPL = 4;
-constexpr int kArNormPullCopyUnits = 4;  // phase 2: 16-byte loads per lane and buffer in flight
 
 // Four waves per SIMD (at most 128 VGPRs): 8 in-process ranks x 64 workgroups of 512 lanes stay co-resident.
 template <int DT, int UPL, int NV>

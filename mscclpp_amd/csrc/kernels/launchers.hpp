@@ -54,6 +54,14 @@ int allReduceRmsNormPullCheck(const mscclppAmdRankView* views, int nviews, int n
                               void* const* resOut, const void* const* gamma, size_t rows, size_t cols, int dtype,
                               int& nblocks, int& nthreads, int* upl, ArNormPullGeom* g);
 int allReduceRmsNormPullDefaultBlocks(int nranks, uint64_t rows, uint64_t cols);
+int launchAllReduceRmsNormQuantPull(const mscclppAmdRankView* views, int nviews, int nranks,
+                                    const void* const* residual, void* const* resOut, void* const* peerResOut,
+                                    const void* const* gamma, void* const* scale, void* const* peerScale, size_t rows,
+                                    size_t cols, int dtype, float eps, int nblocks, int nthreads, uint64_t budget,
+                                    hipStream_t s);
+int allReduceRmsNormQuantPullCheck(const mscclppAmdRankView* views, int nviews, int nranks, const void* const* residual,
+                                   void* const* resOut, const void* const* gamma, void* const* scale, size_t rows,
+                                   size_t cols, int dtype, int& nblocks, int& nthreads, int* upl, ArNormPullGeom* g);
 int launchSendRecv(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdSendRecvOp* ops, int nops,
                    int nblocks, int nthreads, uint64_t budget, hipStream_t s);
 int sendrecvDefaultBlocks(uint64_t bytes);
