@@ -392,6 +392,38 @@ int mscclppAmdAllReduceRmsNormQuantPullCheck(const mscclppAmdRankView* views, in
                                              const void* const* residual, void* const* resOut,
                                              const void* const* gamma, void* const* scale, size_t rows, size_t cols,
                                              int dtype, int nblocks, int nthreads);
+/* That pull with the normalised rows leaving in an OCP microscaling format (kernels/allreduce_rmsnorm_mx_pull.hip;
+ * DESIGN.md §17l): resOut as above, bit for bit; y -- the pull entry point's y at the same (cols, nthreads), bit
+ * for bit -- is not stored.  Per block B of 32 consecutive columns of a row,
+ *   amax = max_{j in B} |y_j|, E = max(e32(amax) - emax, 0), q_j = fmt(y_j * 2^(127 - E))
+ * with e32 the biased exponent field of amax as fp32, emax = 8 (e4m3) or 2 (e2m1) -- the OCP MX v1.0 scale
+ * X = 2^(E - 127) -- an exact fp32 product, and one rounding to nearest even that saturates at +-448 / +-6.
+ * format MSCCLPP_AMD_MX_FP8_E4M3: q (view.output) is [rows][cols] bytes; MSCCLPP_AMD_MX_FP4_E2M1: [rows][cols / 2]
+ * bytes, column 2i in the low and column 2i + 1 in the high nibble of byte i.  scale[i] is [rows][cols / 32] e8m0
+ * bytes E.  q and scale are bit-identical on all ranks, for every grid and from call to call.  An all-zero block
+ * gives E = 0 and q = +-0; a block whose y holds a NaN or an infinity has an unspecified q and E (its resOut, the
+ * other blocks and rows are as defined, and nothing faults).  Views, residual / resOut / peerResOut / gamma,
+ * nblocks and nthreads as for mscclppAmdAllReduceRmsNormPullLaunch, with peerOutput[q] = rank q's q.  scale: a
+ * host array with one entry per view; peerScale: nviews x MSCCLPP_AMD_MAX_RANKS entries, [i *
+ * MSCCLPP_AMD_MAX_RANKS + q] = rank q's scale as view i has it mapped.  resOut[i] == residual[i] is the only
+ * in-place form.
+ * 4: as that entry point, and cols no multiple of 32, an unknown format, a null q or scale, a q that is not
+ * 16-byte aligned, a q or a scale (rows * cols / 32 bytes, any alignment) that overlaps any buffer of any view, or
+ * no peerScale; 5: as that entry point (the limit applies to a workgroup's rows of x). */
+#define MSCCLPP_AMD_MX_FP8_E4M3 0
+#define MSCCLPP_AMD_MX_FP4_E2M1 1
+int mscclppAmdAllReduceRmsNormMxPullLaunch(const mscclppAmdRankView* views, int nviews, int nranks,
+                                           const void* const* residual, void* const* resOut, void* const* peerResOut,
+                                           const void* const* gamma, void* const* scale, void* const* peerScale,
+                                           size_t rows, size_t cols, int dtype, int format, float eps, int nblocks,
+                                           int nthreads, uint64_t budgetTicks, void* stream);
+/* That entry point's answer for the buffers, the shape and the format alone (views: input and output are the only
+ * fields read), host only: 0, 4 or 5 as above, without the views' plumbing, peerResOut, peerScale and the
+ * residency of the grid. */
+int mscclppAmdAllReduceRmsNormMxPullCheck(const mscclppAmdRankView* views, int nviews, int nranks,
+                                          const void* const* residual, void* const* resOut, const void* const* gamma,
+                                          void* const* scale, size_t rows, size_t cols, int dtype, int format,
+                                          int nblocks, int nthreads);
 /* Send / Recv by a zero-copy pull (kernels/sendrecv.hip): one launch runs a table of point-to-point
  * operations, in table order.  An operation moves `bytes` from `send` on rank `src` to `recv` on
  * rank `dst`: the receiver reads `send` -- the address at which the view of rank `dst` has the
@@ -447,7 +479,7 @@ int mscclppAmdTunedConfigSource(const char* collective, int nranks, size_t bytes
 // 3 reduce + all-gather stores issued, 4 end; zero-copy: 0 start, 1 entry handshake done, 2 reduce +
 // all-gather stores issued, 3 end; LL16: 0 start, 1 step 1 (puts), 2 step 2 (reduce + broadcast),
 // 3 step 3 (unpack) done; LL8: 0 start, 1 puts issued, 2 end; AllToAll: 0 start, 1 entry handshake
-// done, 2 segments stored, 3 end; AllToAll LL: 0 start, 1 puts issued, 2 stored; AllReduce+RMSNorm (of a workgroup's last row): 0 start, 1 puts issued, 2 reduced, 3 normalised; AllReduce+RMSNorm pull: 0 start, 1 entry handshake done, 2 own rows normalised, 3 peers' rows gathered, 4 end (its quantising form: the same five); Reduce: 0 start, 1 entry handshake done, 2 result stored (root),
+// done, 2 segments stored, 3 end; AllToAll LL: 0 start, 1 puts issued, 2 stored; AllReduce+RMSNorm (of a workgroup's last row): 0 start, 1 puts issued, 2 reduced, 3 normalised; AllReduce+RMSNorm pull: 0 start, 1 entry handshake done, 2 own rows normalised, 3 peers' rows gathered, 4 end (its two quantising forms: the same five); Reduce: 0 start, 1 entry handshake done, 2 result stored (root),
 // 3 end; Send/Recv: 0 start, 1 readies posted, 2 receives stored, 3 dones seen; pull-reduce (MAX /
 // AVG): 0 start, 1 entry handshake done, 2 own range reduced, 3 peers' slices gathered (AllReduce
 // only), 4 end.  buf = NULL turns it off.  Returns 0,
@@ -485,6 +517,13 @@ int mscclppAmdCommAllReduceRmsNormPull(ncclComm_t comm, const void* x, void* y, 
 int mscclppAmdCommAllReduceRmsNormQuantPull(ncclComm_t comm, const void* x, void* q, float* scale, const void* residual,
                                             void* resOut, const void* gamma, size_t rows, size_t cols, int ncclDtype,
                                             float eps, void* stream);
+/* The microscaling form, mscclppAmdAllReduceRmsNormMxPullLaunch, on this communicator: q is [rows][cols] (MXFP8) or
+ * [rows][cols / 2] (MXFP4) bytes, scale [rows][cols / 32] e8m0 bytes; x, q, scale and resOut are registered as
+ * above, after the arguments are checked.  resOut == residual is the only in-place form.  Every rank must make the
+ * same call.  Refusals as for the launch entry point; also ncclInvalidArgument on a one-rank communicator. */
+int mscclppAmdCommAllReduceRmsNormMxPull(ncclComm_t comm, const void* x, void* q, void* scale, const void* residual,
+                                         void* resOut, const void* gamma, size_t rows, size_t cols, int ncclDtype,
+                                         int format, float eps, void* stream);
 /* Reduce-type code (MSCCLPP_AMD_*) for an ncclDataType_t and accumulation type (-1 = AUTO), or -1. */
 int mscclppAmdReduceType(int ncclDtype, int accumNcclDtype);
 int mscclppAmdCommBarrier(ncclComm_t comm);

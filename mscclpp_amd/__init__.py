@@ -192,6 +192,14 @@ def lib():
                                                      ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), sz, sz,
                                                      i32, i32, i32],
         "mscclppAmdCommAllReduceRmsNormQuantPull": [vp, vp, vp, vp, vp, vp, vp, sz, sz, i32, ctypes.c_float, vp],
+        "mscclppAmdAllReduceRmsNormMxPullLaunch": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(vp),
+                                                   ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                                   ctypes.POINTER(vp), ctypes.POINTER(vp), sz, sz, i32, i32, ctypes.c_float,
+                                                   i32, i32, u64, vp],
+        "mscclppAmdAllReduceRmsNormMxPullCheck": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(vp),
+                                                  ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), sz, sz,
+                                                  i32, i32, i32, i32],
+        "mscclppAmdCommAllReduceRmsNormMxPull": [vp, vp, vp, vp, vp, vp, vp, sz, sz, i32, i32, ctypes.c_float, vp],
         "mscclppAmdCommAllToAllLLCount": [vp, ctypes.POINTER(ctypes.c_uint64)],
         "mscclppAmdReduceLaunch": [ctypes.POINTER(RankView), i32, i32, sz, i32, i32, i32, i32, i32, u64, vp],
         "ncclReduce": [vp, vp, sz, i32, i32, i32, vp, vp],
@@ -408,6 +416,7 @@ TRACE_PHASES = {
     "allreduce_rms_norm": ("put", "reduce", "normalise"),
     "allreduce_rms_norm_pull": ("entry_handshake", "reduce_normalise", "gather", "exit_handshake"),
     "allreduce_rms_norm_quant_pull": ("entry_handshake", "reduce_normalise_quantise", "gather", "exit_handshake"),
+    "allreduce_rms_norm_mx_pull": ("entry_handshake", "reduce_normalise_quantise", "gather", "exit_handshake"),
 }
 
 
@@ -505,6 +514,29 @@ def _rms_norm_quant_tensors(x, q, scale, residual, res_out, gamma):
     if not (ok and scale.is_contiguous()):
         raise MscclppError(4, "all_reduce_rms_norm_quant_pull: q of float8_e4m3fn / uint8 and x's shape, scale of "
                               "float32 and [rows], both contiguous")
+
+
+MX_FORMATS = {"mxfp8": 0, "mxfp4": 1}  # MSCCLPP_AMD_MX_FP8_E4M3, MSCCLPP_AMD_MX_FP4_E2M1
+
+
+def _rms_norm_mx_tensors(x, q, scale, residual, res_out, gamma, fmt):
+    """_rms_norm_tensors for the microscaling entry points -> the format's code: q is uint8 or the format's torch
+    dtype, of [rows, cols] (mxfp8) or [rows, cols // 2] (mxfp4); scale uint8 or float8_e8m0fnu of [rows, cols // 32];
+    both contiguous."""
+    _rms_norm_tensors(x, x, residual, res_out, gamma)
+    if fmt not in MX_FORMATS:
+        raise MscclppError(4, "all_reduce_rms_norm_mx_pull: fmt is 'mxfp8' or 'mxfp4'")
+    named = lambda *names: tuple(getattr(torch, n) for n in names if hasattr(torch, n))
+    rows, cols = x.shape
+    q_types = named("uint8", "float8_e4m3fn") if fmt == "mxfp8" else named("uint8", "float4_e2m1fn_x2")
+    q_shape = (rows, cols) if fmt == "mxfp8" else (rows, cols // 2)
+    ok = cols % 32 == 0 and q is not None and q.dtype in q_types and tuple(q.shape) == q_shape and q.is_contiguous()
+    ok = ok and scale is not None and scale.dtype in named("uint8", "float8_e8m0fnu")
+    if not (ok and tuple(scale.shape) == (rows, cols // 32) and scale.is_contiguous()):
+        raise MscclppError(4, "all_reduce_rms_norm_mx_pull: cols a multiple of 32, q of uint8 or the format's dtype and "
+                              "[rows, cols] (mxfp8) / [rows, cols // 2] (mxfp4), scale of uint8 / float8_e8m0fnu and "
+                              "[rows, cols // 32], both contiguous")
+    return MX_FORMATS[fmt]
 
 
 def all_reduce_rms_norm_scratch_required(nranks, rows, cols, dtype_code):
@@ -752,6 +784,31 @@ class InProcessRanks:
                                                                budget_ticks, stream_ptr(stream))
         check(code, "in-process all_reduce_rms_norm_quant_pull")
 
+    def all_reduce_rms_norm_mx_pull(self, xs, qs, scales, gammas, fmt, residuals=None, res_outs=None, eps=1e-6,
+                                    nblocks=0, nthreads=0, budget_ticks=500_000_000, stream=None):
+        """all_reduce_rms_norm_pull whose normalised rows leave block-scaled (mscclppAmdAllReduceRmsNormMxPullLaunch):
+        fmt "mxfp8" (qs[r]: [rows, cols] e4m3 bytes) or "mxfp4" (qs[r]: [rows, cols // 2] bytes of two e2m1 codes,
+        the even column in the low nibble); scales[r]: [rows, cols // 32] e8m0 bytes E.  Per block of 32 columns
+        E = max(exponent field of max|y| - emax, 0) and q = fmt(y * 2^(127 - E)) of that method's y, which is not
+        stored.  res_outs are that method's bits; qs and scales are equal on all ranks for every grid.
+        cols % 32 == 0; qs and scales overlap nothing, res_outs[r] may be residuals[r]."""
+        for r in range(self.n):
+            fcode = _rms_norm_mx_tensors(xs[r], qs[r], scales[r], residuals and residuals[r], res_outs and res_outs[r],
+                                         gammas[r], fmt)
+            if xs[r].shape != xs[0].shape or xs[r].dtype != xs[0].dtype:
+                raise MscclppError(4, "all_reduce_rms_norm_mx_pull: the ranks' tensors differ in shape or dtype")
+        rows, cols = xs[0].shape
+        ptrs = lambda ts: None if ts is None else (ctypes.c_void_p * self.n)(*[None if t is None else t.data_ptr() for t in ts])
+        peers = lambda ts: None if ts is None else (ctypes.c_void_p * (self.n * MAX_RANKS))(
+            *[ts[q].data_ptr() if q < self.n and ts[q] is not None else None
+              for _ in range(self.n) for q in range(MAX_RANKS)])  # every view sees rank q's buffer at its own address
+        code = lib().mscclppAmdAllReduceRmsNormMxPullLaunch(self.views(xs, qs), self.n, self.n, ptrs(residuals),
+                                                            ptrs(res_outs), peers(res_outs), ptrs(gammas), ptrs(scales),
+                                                            peers(scales), rows, cols, DTYPE_CODES.get(xs[0].dtype, -1),
+                                                            fcode, eps, nblocks, nthreads, budget_ticks,
+                                                            stream_ptr(stream))
+        check(code, "in-process all_reduce_rms_norm_mx_pull")
+
     def send_recv(self, ops, nblocks=0, nthreads=0, budget_ticks=500_000_000, stream=None):
         """ncclSend / ncclRecv (a whole group) for in-process ranks, one launch.  ops: (src, dst, send,
         recv) in table order -- `send` on rank src (a tensor, read in place by rank dst) lands in
@@ -897,6 +954,29 @@ class Communicator:
                                                             ptr(res_out), ptr(gamma), rows, cols,
                                                             NCCL_DTYPES.get(x.dtype, -1), eps, stream_ptr(stream)),
               "mscclppAmdCommAllReduceRmsNormQuantPull")
+        return q, scale, res_out
+
+    def all_reduce_rms_norm_mx_pull(self, x, gamma, fmt, q=None, scale=None, residual=None, res_out=None, eps=1e-6,
+                                    stream=None):
+        """all_reduce_rms_norm_pull with its y block-scaled for an MXFP8 / MXFP4 linear layer
+        (mscclppAmdCommAllReduceRmsNormMxPull): fmt "mxfp8" (q: uint8 or float8_e4m3fn, [rows, cols]) or "mxfp4" (q:
+        uint8 or float4_e2m1fn_x2, [rows, cols // 2]); scale: uint8 or float8_e8m0fnu, [rows, cols // 32], one byte
+        E per block of 32 columns: q = fmt(y * 2^(127 - E)).  Both default to new uint8 tensors.  y is not stored;
+        res_out defaults to the residual.  x.shape[1] % 32 == 0.  x, q, scale and res_out are registered on first use
+        (collective), so pass the same q and scale again where the call repeats.  Returns (q, scale, res_out)."""
+        if x is not None and x.dim() == 2 and fmt in MX_FORMATS:
+            new = lambda c: torch.empty((x.shape[0], c), dtype=torch.uint8, device=x.device)
+            q = new(x.shape[1] // (1 if fmt == "mxfp8" else 2)) if q is None else q
+            scale = new(x.shape[1] // 32) if scale is None else scale
+        if residual is not None and res_out is None:
+            res_out = residual
+        code = _rms_norm_mx_tensors(x, q, scale, residual, res_out, gamma, fmt)
+        rows, cols = x.shape
+        ptr = lambda t: ctypes.c_void_p(None if t is None else t.data_ptr())
+        check(lib().mscclppAmdCommAllReduceRmsNormMxPull(self.comm, ptr(x), ptr(q), ptr(scale), ptr(residual),
+                                                         ptr(res_out), ptr(gamma), rows, cols,
+                                                         NCCL_DTYPES.get(x.dtype, -1), code, eps, stream_ptr(stream)),
+              "mscclppAmdCommAllReduceRmsNormMxPull")
         return q, scale, res_out
 
     def reduce_scatter(self, send, recv, op="sum", stream=None):

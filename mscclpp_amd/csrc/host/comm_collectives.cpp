@@ -344,6 +344,31 @@ int ncclComm::allReduceRmsNormQuantPull(const void* x, void* q, float* scale, co
   return rc;
 }
 
+int ncclComm::allReduceRmsNormMxPull(const void* x, void* q, void* scale, const void* residual, void* resOut,
+                                     const void* gamma, size_t rows, size_t cols, int dtype, int format, float eps,
+                                     hipStream_t stream) {
+  std::lock_guard<std::mutex> lk(mu);
+  mscclppAmdRankView v = baseView(x, q);
+  const void* const* res = residual || resOut ? &residual : nullptr;
+  void* const* ro = residual || resOut ? &resOut : nullptr;
+  // As allReduceRmsNormQuantPull: refused before anything is registered and before any device call, on the
+  // arguments alone, so every rank refuses alike.
+  int nblocks = 0, nthreads = 0;
+  if (const int rc = allReduceRmsNormMxPullCheck(&v, 1, nranks, res, ro, &gamma, &scale, rows, cols, dtype, format,
+                                                 nblocks, nthreads, nullptr, nullptr))
+    return rc;
+  v = pullView(x, q, stream);  // the peers read x, and this rank's finished rows out of q, scale and resOut
+  const auto outs = registerOutput(q, stream);
+  for (int r = 0; r < nranks; ++r) v.peerOutput[r] = outs[r];
+  std::array<void*, MSCCLPP_AMD_MAX_RANKS> peerScale = registerOutput(scale, stream), peerResOut{};
+  if (residual) peerResOut = registerOutput(resOut, stream);
+  const int rc = launchAllReduceRmsNormMxPull(&v, 1, nranks, res, ro, residual ? peerResOut.data() : nullptr, &gamma,
+                                              &scale, peerScale.data(), rows, cols, dtype, format, eps, 0, 0,
+                                              spinBudgetTicks(), stream);
+  mappings.recordUses(stream, device);
+  return rc;
+}
+
 ncclRedOp_t ncclComm::preMulCreate(const PreMulOp& e) {
   std::lock_guard<std::mutex> lk(mu);
   size_t slot = 0;

@@ -510,6 +510,12 @@ struct ncclComm {
   // scale overlap nothing, so there is no in-place form but resOut == residual.
   int allReduceRmsNormQuantPull(const void* x, void* q, float* scale, const void* residual, void* resOut,
                                 const void* gamma, size_t rows, size_t cols, int dtype, float eps, hipStream_t stream);
+  // That kernel with y leaving block-scaled, MXFP8 or MXFP4 bytes `q` and one e8m0 byte per 32 columns in `scale`
+  // (kernels/allreduce_rmsnorm_mx_pull.hip): x, q, scale and resOut are registered; q and scale
+  // overlap nothing, so there is no in-place form but resOut == residual.
+  int allReduceRmsNormMxPull(const void* x, void* q, void* scale, const void* residual, void* resOut,
+                             const void* gamma, size_t rows, size_t cols, int dtype, int format, float eps,
+                             hipStream_t stream);
   ncclRedOp_t preMulCreate(const PreMulOp& e);
   // The live entry of `op` (a copy: the caller launches after the lock is dropped, and the handle may
   // be destroyed as soon as the collective call has returned), or false.

@@ -952,6 +952,53 @@ int mscclppAmdCommAllReduceRmsNormQuantPull(ncclComm_t comm, const void* x, void
   });
 }
 
+// The pull kernel with y leaving as MXFP8 / MXFP4 and one e8m0 byte per 32 columns
+// (kernels/allreduce_rmsnorm_mx_pull.hip): the views' plumbing is checked here, the buffers, the
+// shape, the format, peerResOut and peerScale by launchAllReduceRmsNormMxPull, all before a device is touched; a
+// refusal launches nothing.
+int mscclppAmdAllReduceRmsNormMxPullLaunch(const mscclppAmdRankView* views, int nviews, int nranks,
+                                           const void* const* residual, void* const* resOut, void* const* peerResOut,
+                                           const void* const* gamma, void* const* scale, void* const* peerScale,
+                                           size_t rows, size_t cols, int dtype, int format, float eps, int nblocks,
+                                           int nthreads, uint64_t budgetTicks, void* stream) {
+  return guarded([&] {
+    ViewNeeds needs;
+    needs.all = kViewInput | kViewOutput | kViewHandshake | kViewPeerInput | kViewPeerOutput;
+    if (!gamma || !viewsValid(views, nviews, nranks, needs)) return (int)ncclInvalidArgument;
+    unsigned seen = 0;
+    for (int i = 0; i < nviews; ++i) {  // no rank twice
+      if ((seen >> views[i].rank) & 1u) return (int)ncclInvalidArgument;
+      seen |= 1u << views[i].rank;
+    }
+    return mscclpp_amd::launchAllReduceRmsNormMxPull(views, nviews, nranks, residual, resOut, peerResOut, gamma, scale,
+                                                     peerScale, rows, cols, dtype, format, eps, nblocks, nthreads,
+                                                     budgetTicks ? budgetTicks : spinBudgetTicks(),
+                                                     (hipStream_t)stream);
+  });
+}
+
+int mscclppAmdAllReduceRmsNormMxPullCheck(const mscclppAmdRankView* views, int nviews, int nranks,
+                                          const void* const* residual, void* const* resOut, const void* const* gamma,
+                                          void* const* scale, size_t rows, size_t cols, int dtype, int format,
+                                          int nblocks, int nthreads) {
+  return guarded([&] {
+    return mscclpp_amd::allReduceRmsNormMxPullCheck(views, nviews, nranks, residual, resOut, gamma, scale, rows, cols,
+                                                    dtype, format, nblocks, nthreads, nullptr, nullptr);
+  });
+}
+
+int mscclppAmdCommAllReduceRmsNormMxPull(ncclComm_t comm, const void* x, void* q, void* scale, const void* residual,
+                                         void* resOut, const void* gamma, size_t rows, size_t cols, int ncclDtype,
+                                         int format, float eps, void* stream) {
+  return guarded([&] {
+    if (!comm || comm->nranks < 2) return (int)ncclInvalidArgument;  // (one rank: refused, as §17i)
+    const int dt = ncclDtype == (int)ncclFloat16 ? MSCCLPP_AMD_F16 : ncclDtype == (int)ncclBfloat16 ? MSCCLPP_AMD_BF16 : -1;
+    if (dt < 0) return (int)ncclInvalidArgument;
+    return comm->allReduceRmsNormMxPull(x, q, scale, residual, resOut, gamma, rows, cols, dt, format, eps,
+                                        (hipStream_t)stream);
+  });
+}
+
 int mscclppAmdCommAllToAllLLCount(ncclComm_t comm, uint64_t* count) {
   if (!comm || !count) return ncclInvalidArgument;
   std::lock_guard<std::mutex> lk(comm->mu);

@@ -1,6 +1,7 @@
 // What the fused AllReduce + residual add + RMSNorm kernels share (allreduce_rmsnorm_ll.hip,
-// allreduce_rmsnorm_pull.hip, allreduce_rmsnorm_quant_pull.hip): the element decode / encode of the definition
-// (DESIGN.md §17i), the geometry of the two pull kernels and the host's check of a call's buffers.
+// allreduce_rmsnorm_pull.hip, allreduce_rmsnorm_quant_pull.hip, allreduce_rmsnorm_mx_pull.hip): the element decode
+// / encode of the definition, the e4m3 conversion of the two quantising kernels, the geometry of
+// the pull kernels and the host's check of a call's buffers.
 #pragma once
 
 #include "common.hpp"
@@ -36,7 +37,30 @@ __device__ __forceinline__ uint32_t arnorm_pack(float lo, float hi) {
   }
 }
 
-// The two-shot pull kernels' (allreduce_rmsnorm_pull.hip, allreduce_rmsnorm_quant_pull.hip) one statement of
+typedef uint16_t arnorm_u16x2 __attribute__((ext_vector_type(2)));
+
+// fp8_sat<false> (reduce_device.hpp) with its bound in ONE scalar register: v_med3_f32 takes sat and -sat off the
+// same operand, where the two literals 448 and -448 cost a VGPR held across the row loop.
+__device__ __forceinline__ float arnorm_sat448(float v, float sat) {
+  if ((__builtin_bit_cast(uint32_t, v) & 0x7f800000u) != 0x7f800000u) v = __builtin_amdgcn_fmed3f(v, sat, -sat);
+  return v;
+}
+
+// Two DT elements of y times inv, clamped to +-448 and rounded (RNE) into byte pair `Hi` of `old`.
+template <int DT, bool Hi>
+__device__ __forceinline__ uint32_t arnorm_quant2(uint32_t yw, float inv, float sat, uint32_t old) {
+  const float lo = arnorm_sat448(fp32_product(arnorm_lo<DT>(yw), inv), sat);
+  const float hi = arnorm_sat448(fp32_product(arnorm_hi<DT>(yw), inv), sat);
+  return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(lo, hi, (int)old, Hi);
+}
+
+// __shfl_xor(v, m, 64) with the partner lane taken from threadIdx.x, which is live anyway, instead of a lane
+// index held across the row loop: the same lanes, so the same sums in the same order.
+__device__ __forceinline__ uint32_t arnorm_xor_lane(uint32_t v, int m, uint32_t t) {
+  return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((t ^ (uint32_t)m) & 63u) << 2), (int)v);
+}
+
+// The two-shot pull kernels' (allreduce_rmsnorm_pull.hip and its two quantising forms) one statement of
 // the geometry; the host's checks, the launchers and the kernels use it.
 struct ArNormPullGeom {
   uint32_t rows;

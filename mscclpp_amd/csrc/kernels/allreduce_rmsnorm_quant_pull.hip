@@ -52,29 +52,6 @@ struct ArNormQuantPullArgs {
 static_assert(sizeof(ArNormQuantPullArgs<kMaxRanks>) <= 4096,
               "in-process AllReduce+RMSNorm quantising pull arguments exceed the kernel-argument limit");
 
-typedef uint16_t arnorm_u16x2 __attribute__((ext_vector_type(2)));
-
-// fp8_sat<false> (reduce_device.hpp) with its bound in ONE scalar register: v_med3_f32 takes sat and -sat off the
-// same operand, where the two literals 448 and -448 cost a VGPR held across the row loop.
-__device__ __forceinline__ float arnorm_sat448(float v, float sat) {
-  if ((__builtin_bit_cast(uint32_t, v) & 0x7f800000u) != 0x7f800000u) v = __builtin_amdgcn_fmed3f(v, sat, -sat);
-  return v;
-}
-
-// Two DT elements of y times inv, clamped to +-448 and rounded (RNE) into byte pair `Hi` of `old`.
-template <int DT, bool Hi>
-__device__ __forceinline__ uint32_t arnorm_quant2(uint32_t yw, float inv, float sat, uint32_t old) {
-  const float lo = arnorm_sat448(fp32_product(arnorm_lo<DT>(yw), inv), sat);
-  const float hi = arnorm_sat448(fp32_product(arnorm_hi<DT>(yw), inv), sat);
-  return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(lo, hi, (int)old, Hi);
-}
-
-// __shfl_xor(v, m, 64) with the partner lane taken from threadIdx.x, which is live anyway, instead of a lane
-// index held across the row loop: the same lanes, so the same sums in the same order.
-__device__ __forceinline__ uint32_t arnorm_xor_lane(uint32_t v, int m, uint32_t t) {
-  return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((t ^ (uint32_t)m) & 63u) << 2), (int)v);
-}
-
 // Four waves per SIMD (at most 128 VGPRs), as allreduceRmsNormPullKernel.
 template <int DT, int UPL, int NV>
 __global__ void __launch_bounds__(512, 4) allreduceRmsNormQuantPullKernel(ArNormQuantPullArgs<NV> a) {
