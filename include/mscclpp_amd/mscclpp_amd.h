@@ -424,6 +424,32 @@ int mscclppAmdAllReduceRmsNormMxPullCheck(const mscclppAmdRankView* views, int n
                                           const void* const* residual, void* const* resOut, const void* const* gamma,
                                           void* const* scale, size_t rows, size_t cols, int dtype, int format,
                                           int nblocks, int nthreads);
+/* mscclppAmdAllReduceRmsNormLaunch -- the one hop of LL8 packets for DECODE sizes, with its views, scratch, flags,
+ * size cap (in bytes of x) and refusals -- with the normalised rows leaving quantised
+ * (kernels/allreduce_rmsnorm_quant_ll.hip): resOut as that entry point's, bit for bit; y -- that
+ * entry point's y at the same (cols, nthreads), bit for bit -- is not stored.  format MSCCLPP_AMD_QUANT_FP8_ROW: q
+ * (view.output) and scale as defined for mscclppAmdAllReduceRmsNormQuantPullLaunch ([rows][cols] e4m3 bytes,
+ * [rows] floats); MSCCLPP_AMD_MX_FP8_E4M3 / MSCCLPP_AMD_MX_FP4_E2M1: as defined for
+ * mscclppAmdAllReduceRmsNormMxPullLaunch ([rows][cols] or [rows][cols / 2] bytes, [rows][cols / 32] e8m0 bytes).
+ * Every rank computes every row in one order, so q and scale are bit-identical on all ranks, for every grid and
+ * from call to call; nothing is gathered and nothing need be registered.  All-zero and non-finite rows / blocks
+ * behave as for those two entry points.  scale: a host array with one entry per view.  resOut[i] == residual[i]
+ * is the only in-place form.
+ * 4: as mscclppAmdAllReduceRmsNormLaunch, and an unknown format, cols no multiple of 32 in an MX format, a null q
+ * or scale, a q or an FP8_ROW scale that is not 4-byte aligned (MX scale bytes: any alignment), a q or a scale
+ * that overlaps any buffer of any view; 5: as that entry point. */
+#define MSCCLPP_AMD_QUANT_FP8_ROW 2
+int mscclppAmdAllReduceRmsNormQuantLaunch(const mscclppAmdRankView* views, int nviews, int nranks,
+                                          const void* const* residual, void* const* resOut, const void* const* gamma,
+                                          void* const* scale, size_t rows, size_t cols, int dtype, int format,
+                                          float eps, int nblocks, int nthreads, uint64_t budgetTicks, void* stream);
+/* That entry point's answer for the buffers, the shape and the format alone (views: input and output are the only
+ * fields read), host only: 0, 4 or 5 as above, without the views' plumbing, the scratch and the residency of the
+ * grid. */
+int mscclppAmdAllReduceRmsNormQuantCheck(const mscclppAmdRankView* views, int nviews, int nranks,
+                                         const void* const* residual, void* const* resOut, const void* const* gamma,
+                                         void* const* scale, size_t rows, size_t cols, int dtype, int format,
+                                         int nblocks, int nthreads);
 /* Send / Recv by a zero-copy pull (kernels/sendrecv.hip): one launch runs a table of point-to-point
  * operations, in table order.  An operation moves `bytes` from `send` on rank `src` to `recv` on
  * rank `dst`: the receiver reads `send` -- the address at which the view of rank `dst` has the
@@ -524,6 +550,16 @@ int mscclppAmdCommAllReduceRmsNormQuantPull(ncclComm_t comm, const void* x, void
 int mscclppAmdCommAllReduceRmsNormMxPull(ncclComm_t comm, const void* x, void* q, void* scale, const void* residual,
                                          void* resOut, const void* gamma, size_t rows, size_t cols, int ncclDtype,
                                          int format, float eps, void* stream);
+/* The quantising form of mscclppAmdCommAllReduceRmsNorm for decode sizes, mscclppAmdAllReduceRmsNormQuantLaunch, on
+ * this communicator's LL scratch and flags: format MSCCLPP_AMD_QUANT_FP8_ROW (q [rows][cols] e4m3 bytes, scale
+ * [rows] floats), MSCCLPP_AMD_MX_FP8_E4M3 or MSCCLPP_AMD_MX_FP4_E2M1 (q [rows][cols] or [rows][cols / 2] bytes,
+ * scale [rows][cols / 32] e8m0 bytes).  Nothing is registered and no host traffic runs; resOut == residual is the
+ * only in-place form.  Every rank must make the same call.  Refusals as for the launch entry point; also
+ * ncclInvalidArgument on a one-rank communicator, and ncclInvalidUsage under stream capture when the scratch
+ * would have to grow. */
+int mscclppAmdCommAllReduceRmsNormQuant(ncclComm_t comm, const void* x, void* q, void* scale, const void* residual,
+                                        void* resOut, const void* gamma, size_t rows, size_t cols, int ncclDtype,
+                                        int format, float eps, void* stream);
 /* Reduce-type code (MSCCLPP_AMD_*) for an ncclDataType_t and accumulation type (-1 = AUTO), or -1. */
 int mscclppAmdReduceType(int ncclDtype, int accumNcclDtype);
 int mscclppAmdCommBarrier(ncclComm_t comm);

@@ -200,6 +200,13 @@ def lib():
                                                   ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), sz, sz,
                                                   i32, i32, i32, i32],
         "mscclppAmdCommAllReduceRmsNormMxPull": [vp, vp, vp, vp, vp, vp, vp, sz, sz, i32, i32, ctypes.c_float, vp],
+        "mscclppAmdAllReduceRmsNormQuantLaunch": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(vp),
+                                                  ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), sz, sz, i32,
+                                                  i32, ctypes.c_float, i32, i32, u64, vp],
+        "mscclppAmdAllReduceRmsNormQuantCheck": [ctypes.POINTER(RankView), i32, i32, ctypes.POINTER(vp),
+                                                 ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), sz, sz, i32,
+                                                 i32, i32, i32],
+        "mscclppAmdCommAllReduceRmsNormQuant": [vp, vp, vp, vp, vp, vp, vp, sz, sz, i32, i32, ctypes.c_float, vp],
         "mscclppAmdCommAllToAllLLCount": [vp, ctypes.POINTER(ctypes.c_uint64)],
         "mscclppAmdReduceLaunch": [ctypes.POINTER(RankView), i32, i32, sz, i32, i32, i32, i32, i32, u64, vp],
         "ncclReduce": [vp, vp, sz, i32, i32, i32, vp, vp],
@@ -539,6 +546,21 @@ def _rms_norm_mx_tensors(x, q, scale, residual, res_out, gamma, fmt):
     return MX_FORMATS[fmt]
 
 
+QUANT_FORMATS = dict(MX_FORMATS, fp8_row=2)  # ..., MSCCLPP_AMD_QUANT_FP8_ROW
+
+
+def _rms_norm_any_quant_tensors(x, q, scale, residual, res_out, gamma, fmt):
+    """The tensor checks of all_reduce_rms_norm_quant -> the format's code: "fp8_row" takes the tensors of
+    all_reduce_rms_norm_quant_pull, "mxfp8" / "mxfp4" those of all_reduce_rms_norm_mx_pull."""
+    if fmt == "fp8_row":
+        _rms_norm_quant_tensors(x, q, scale, residual, res_out, gamma)
+    elif fmt in MX_FORMATS:
+        _rms_norm_mx_tensors(x, q, scale, residual, res_out, gamma, fmt)
+    else:
+        raise MscclppError(4, "all_reduce_rms_norm_quant: fmt is 'fp8_row', 'mxfp8' or 'mxfp4'")
+    return QUANT_FORMATS[fmt]
+
+
 def all_reduce_rms_norm_scratch_required(nranks, rows, cols, dtype_code):
     """Scratch bytes per rank InProcessRanks.all_reduce_rms_norm needs for [rows][cols]; 0: not carried."""
     return lib().mscclppAmdAllReduceRmsNormScratchRequired(nranks, rows, cols, dtype_code)
@@ -809,6 +831,27 @@ class InProcessRanks:
                                                             stream_ptr(stream))
         check(code, "in-process all_reduce_rms_norm_mx_pull")
 
+    def all_reduce_rms_norm_quant(self, xs, qs, scales, gammas, fmt, residuals=None, res_outs=None, eps=1e-6, nblocks=0,
+                                  nthreads=0, budget_ticks=500_000_000, stream=None):
+        """all_reduce_rms_norm -- the one hop of LL8 packets for decode sizes, its scratch, cap and res_outs -- whose
+        normalised rows leave quantised (mscclppAmdAllReduceRmsNormQuantLaunch): fmt "fp8_row" (qs, scales as for
+        all_reduce_rms_norm_quant_pull), "mxfp8" or "mxfp4" (as for all_reduce_rms_norm_mx_pull), of that method's y
+        at the same (cols, nthreads), which is not stored.  Every rank quantises every row itself: nothing is
+        gathered.  qs and scales are equal on all ranks for every grid; they overlap nothing, res_outs[r] may be
+        residuals[r]."""
+        for r in range(self.n):
+            fcode = _rms_norm_any_quant_tensors(xs[r], qs[r], scales[r], residuals and residuals[r],
+                                                res_outs and res_outs[r], gammas[r], fmt)
+            if xs[r].shape != xs[0].shape or xs[r].dtype != xs[0].dtype:
+                raise MscclppError(4, "all_reduce_rms_norm_quant: the ranks' tensors differ in shape or dtype")
+        rows, cols = xs[0].shape
+        ptrs = lambda ts: None if ts is None else (ctypes.c_void_p * self.n)(*[None if t is None else t.data_ptr() for t in ts])
+        code = lib().mscclppAmdAllReduceRmsNormQuantLaunch(self.views(xs, qs), self.n, self.n, ptrs(residuals),
+                                                           ptrs(res_outs), ptrs(gammas), ptrs(scales), rows, cols,
+                                                           DTYPE_CODES.get(xs[0].dtype, -1), fcode, eps, nblocks,
+                                                           nthreads, budget_ticks, stream_ptr(stream))
+        check(code, "in-process all_reduce_rms_norm_quant")
+
     def send_recv(self, ops, nblocks=0, nthreads=0, budget_ticks=500_000_000, stream=None):
         """ncclSend / ncclRecv (a whole group) for in-process ranks, one launch.  ops: (src, dst, send,
         recv) in table order -- `send` on rank src (a tensor, read in place by rank dst) lands in
@@ -977,6 +1020,33 @@ class Communicator:
                                                          ptr(res_out), ptr(gamma), rows, cols,
                                                          NCCL_DTYPES.get(x.dtype, -1), code, eps, stream_ptr(stream)),
               "mscclppAmdCommAllReduceRmsNormMxPull")
+        return q, scale, res_out
+
+    def all_reduce_rms_norm_quant(self, x, gamma, fmt, q=None, scale=None, residual=None, res_out=None, eps=1e-6,
+                                  stream=None):
+        """all_reduce_rms_norm for decode sizes with its y quantised in the same launch
+        (mscclppAmdCommAllReduceRmsNormQuant): fmt "fp8_row" (q, scale and their defaults as for
+        all_reduce_rms_norm_quant_pull), "mxfp8" or "mxfp4" (as for all_reduce_rms_norm_mx_pull).  y is not stored;
+        res_out defaults to the residual.  Nothing is registered and no host traffic runs.  Returns (q, scale,
+        res_out)."""
+        if x is not None and x.dim() == 2 and fmt in QUANT_FORMATS:
+            rows, cols = x.shape
+            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=x.device)
+            if fmt == "fp8_row":
+                q = new((rows, cols), torch.float8_e4m3fn) if q is None else q
+                scale = new((rows,), torch.float32) if scale is None else scale
+            else:
+                q = new((rows, cols // (1 if fmt == "mxfp8" else 2)), torch.uint8) if q is None else q
+                scale = new((rows, cols // 32), torch.uint8) if scale is None else scale
+        if residual is not None and res_out is None:
+            res_out = residual
+        code = _rms_norm_any_quant_tensors(x, q, scale, residual, res_out, gamma, fmt)
+        rows, cols = x.shape
+        ptr = lambda t: ctypes.c_void_p(None if t is None else t.data_ptr())
+        check(lib().mscclppAmdCommAllReduceRmsNormQuant(self.comm, ptr(x), ptr(q), ptr(scale), ptr(residual),
+                                                        ptr(res_out), ptr(gamma), rows, cols,
+                                                        NCCL_DTYPES.get(x.dtype, -1), code, eps, stream_ptr(stream)),
+              "mscclppAmdCommAllReduceRmsNormQuant")
         return q, scale, res_out
 
     def reduce_scatter(self, send, recv, op="sum", stream=None):

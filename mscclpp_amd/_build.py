@@ -58,7 +58,8 @@ def _run(cmd):
 # scalar fp32 instruction.  It costs no register, scratch or occupancy there.
 _NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 NO_PACKED_FP32 = {"allreduce_rmsnorm_ll.hip": _NO_PK, "allreduce_rmsnorm_pull.hip": _NO_PK,
-                  "allreduce_rmsnorm_quant_pull.hip": _NO_PK, "allreduce_rmsnorm_mx_pull.hip": _NO_PK}
+                  "allreduce_rmsnorm_quant_pull.hip": _NO_PK, "allreduce_rmsnorm_mx_pull.hip": _NO_PK,
+                  "allreduce_rmsnorm_quant_ll.hip": _NO_PK}
 
 
 def _compile(src, hdrs):

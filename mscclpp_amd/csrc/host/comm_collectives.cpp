@@ -369,6 +369,36 @@ int ncclComm::allReduceRmsNormMxPull(const void* x, void* q, void* scale, const 
   return rc;
 }
 
+int ncclComm::allReduceRmsNormQuant(const void* x, void* q, void* scale, const void* residual, void* resOut,
+                                    const void* gamma, size_t rows, size_t cols, int dtype, int format, float eps,
+                                    hipStream_t stream) {
+  std::lock_guard<std::mutex> lk(mu);
+  mscclppAmdRankView v = baseView(x, q);
+  const void* const* res = residual || resOut ? &residual : nullptr;
+  void* const* ro = residual || resOut ? &resOut : nullptr;
+  // As allReduceRmsNorm: refused before the communicator's bookkeeping and before any device call, on the
+  // arguments alone, so every rank refuses alike.
+  int nthreads = 0;
+  if (const int rc = allReduceRmsNormQuantCheck(&v, 1, nranks, res, ro, &gamma, &scale, rows, cols, dtype, format, 0,
+                                                nthreads, nullptr))
+    return rc;
+  // (the guard of allReduceRmsNorm: the scratch is that call's, and no call grows it today)
+  const size_t need = allReduceRmsNormScratchRequired(nranks, rows, cols, dtype);
+  if (need > llBytes && streamCapturing(stream)) {
+    warn("AllReduce+RMSNorm under stream capture: the LL scratch would have to grow");
+    return ncclInvalidUsage;
+  }
+  mappings.beginLaunch();
+  ensure(llScratch, llBytes, peerLL, need, stream);
+  v.scratch = llScratch;
+  v.scratchBytes = llBytes;
+  for (int r = 0; r < nranks; ++r) v.peerScratch[r] = peerLL[r];
+  const int rc = launchAllReduceRmsNormQuant(&v, 1, nranks, res, ro, &gamma, &scale, rows, cols, dtype, format, eps, 0, 0,
+                                             spinBudgetTicks(), stream);
+  mappings.recordUses(stream, device);
+  return rc;
+}
+
 ncclRedOp_t ncclComm::preMulCreate(const PreMulOp& e) {
   std::lock_guard<std::mutex> lk(mu);
   size_t slot = 0;

@@ -516,6 +516,12 @@ struct ncclComm {
   int allReduceRmsNormMxPull(const void* x, void* q, void* scale, const void* residual, void* resOut,
                              const void* gamma, size_t rows, size_t cols, int dtype, int format, float eps,
                              hipStream_t stream);
+  // allReduceRmsNorm with y leaving quantised -- per-row FP8 (`scale`: one fp32 per row), MXFP8 or MXFP4 (`scale`:
+  // one e8m0 byte per 32 columns) -- out of the registers that reduced the row
+  // (kernels/allreduce_rmsnorm_quant_ll.hip): shaped like allReduceRmsNorm, the LL scratch and
+  // flags, nothing registered.  format: MSCCLPP_AMD_QUANT_FP8_ROW / _MX_FP8_E4M3 / _MX_FP4_E2M1.
+  int allReduceRmsNormQuant(const void* x, void* q, void* scale, const void* residual, void* resOut, const void* gamma,
+                            size_t rows, size_t cols, int dtype, int format, float eps, hipStream_t stream);
   ncclRedOp_t preMulCreate(const PreMulOp& e);
   // The live entry of `op` (a copy: the caller launches after the lock is dropped, and the handle may
   // be destroyed as soon as the collective call has returned), or false.

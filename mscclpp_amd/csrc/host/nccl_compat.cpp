@@ -999,6 +999,52 @@ int mscclppAmdCommAllReduceRmsNormMxPull(ncclComm_t comm, const void* x, void* q
   });
 }
 
+// The LL kernel with y leaving as per-row FP8, MXFP8 or MXFP4 (kernels/allreduce_rmsnorm_quant_ll.hip; DESIGN.md
+// §17m): the views' plumbing is checked here as for mscclppAmdAllReduceRmsNormLaunch, the buffers, the shape and
+// the format by launchAllReduceRmsNormQuant, all before a device is touched; a refusal launches nothing.
+int mscclppAmdAllReduceRmsNormQuantLaunch(const mscclppAmdRankView* views, int nviews, int nranks,
+                                          const void* const* residual, void* const* resOut, const void* const* gamma,
+                                          void* const* scale, size_t rows, size_t cols, int dtype, int format,
+                                          float eps, int nblocks, int nthreads, uint64_t budgetTicks, void* stream) {
+  return guarded([&] {
+    ViewNeeds needs;
+    needs.all = kViewInput | kViewOutput | kViewScratch | kViewFlags | kViewErr | kViewPeerScratch;
+    if (!gamma || !viewsValid(views, nviews, nranks, needs)) return (int)ncclInvalidArgument;
+    unsigned seen = 0;
+    for (int i = 0; i < nviews; ++i) {
+      const mscclppAmdRankView& v = views[i];
+      if ((seen >> v.rank) & 1u) return (int)ncclInvalidArgument;  // no rank twice
+      seen |= 1u << v.rank;
+      if ((uintptr_t)v.flags % 16) return (int)ncclInvalidArgument;  // 16-byte flag refresh
+    }
+    return mscclpp_amd::launchAllReduceRmsNormQuant(views, nviews, nranks, residual, resOut, gamma, scale, rows, cols,
+                                                    dtype, format, eps, nblocks, nthreads,
+                                                    budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream);
+  });
+}
+
+int mscclppAmdAllReduceRmsNormQuantCheck(const mscclppAmdRankView* views, int nviews, int nranks,
+                                         const void* const* residual, void* const* resOut, const void* const* gamma,
+                                         void* const* scale, size_t rows, size_t cols, int dtype, int format,
+                                         int nblocks, int nthreads) {
+  return guarded([&] {
+    return mscclpp_amd::allReduceRmsNormQuantCheck(views, nviews, nranks, residual, resOut, gamma, scale, rows, cols,
+                                                   dtype, format, nblocks, nthreads, nullptr);
+  });
+}
+
+int mscclppAmdCommAllReduceRmsNormQuant(ncclComm_t comm, const void* x, void* q, void* scale, const void* residual,
+                                        void* resOut, const void* gamma, size_t rows, size_t cols, int ncclDtype,
+                                        int format, float eps, void* stream) {
+  return guarded([&] {
+    if (!comm || comm->nranks < 2) return (int)ncclInvalidArgument;  // (one rank: refused, as §17i)
+    const int dt = ncclDtype == (int)ncclFloat16 ? MSCCLPP_AMD_F16 : ncclDtype == (int)ncclBfloat16 ? MSCCLPP_AMD_BF16 : -1;
+    if (dt < 0) return (int)ncclInvalidArgument;
+    return comm->allReduceRmsNormQuant(x, q, scale, residual, resOut, gamma, rows, cols, dt, format, eps,
+                                       (hipStream_t)stream);
+  });
+}
+
 int mscclppAmdCommAllToAllLLCount(ncclComm_t comm, uint64_t* count) {
   if (!comm || !count) return ncclInvalidArgument;
   std::lock_guard<std::mutex> lk(comm->mu);

@@ -1,7 +1,8 @@
 // What the fused AllReduce + residual add + RMSNorm kernels share (allreduce_rmsnorm_ll.hip,
-// allreduce_rmsnorm_pull.hip, allreduce_rmsnorm_quant_pull.hip, allreduce_rmsnorm_mx_pull.hip): the element decode
-// / encode of the definition, the e4m3 conversion of the two quantising kernels, the geometry of
-// the pull kernels and the host's check of a call's buffers.
+// allreduce_rmsnorm_pull.hip, allreduce_rmsnorm_quant_pull.hip, allreduce_rmsnorm_mx_pull.hip,
+// allreduce_rmsnorm_quant_ll.hip): the element decode / encode of the definition, the e4m3
+// conversion and the block maximum of the quantising kernels, the geometry of the pull kernels and the host's
+// check of a call's buffers.
 #pragma once
 
 #include "common.hpp"
@@ -58,6 +59,18 @@ __device__ __forceinline__ uint32_t arnorm_quant2(uint32_t yw, float inv, float 
 // index held across the row loop: the same lanes, so the same sums in the same order.
 __device__ __forceinline__ uint32_t arnorm_xor_lane(uint32_t v, int m, uint32_t t) {
   return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((t ^ (uint32_t)m) & 63u) << 2), (int)v);
+}
+
+// The microscaling formats of the block-scaling kernels (allreduce_rmsnorm_mx_pull.hip,
+// allreduce_rmsnorm_quant_ll.hip).
+constexpr int kMxFp8 = MSCCLPP_AMD_MX_FP8_E4M3, kMxFp4 = MSCCLPP_AMD_MX_FP4_E2M1;
+
+// The maximum of v over the quad of lanes t ^ 1, t ^ 2 (DPP quad_perm [1,0,3,2], then [2,3,0,1]).
+__device__ __forceinline__ uint32_t arnorm_quad_max(uint32_t v) {
+  uint32_t o = (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xb1, 0xf, 0xf, true);
+  v = v > o ? v : o;
+  o = (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4e, 0xf, 0xf, true);
+  return v > o ? v : o;
 }
 
 // The two-shot pull kernels' (allreduce_rmsnorm_pull.hip and its two quantising forms) one statement of

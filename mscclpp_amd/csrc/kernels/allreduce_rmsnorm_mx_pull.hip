@@ -35,8 +35,6 @@
 
 namespace mscclpp_amd {
 
-constexpr int kMxFp8 = MSCCLPP_AMD_MX_FP8_E4M3, kMxFp4 = MSCCLPP_AMD_MX_FP4_E2M1;
-
 template <int NV>
 struct ArNormMxPullArgs {
   Views<NV> views;           // output: q
@@ -56,14 +54,6 @@ struct ArNormMxPullArgs {
 };
 static_assert(sizeof(ArNormMxPullArgs<kMaxRanks>) <= 4096,
               "in-process AllReduce+RMSNorm MX pull arguments exceed the kernel-argument limit");
-
-// The maximum of v over the quad of lanes t ^ 1, t ^ 2 (DPP quad_perm [1,0,3,2], then [2,3,0,1]).
-__device__ __forceinline__ uint32_t arnorm_quad_max(uint32_t v) {
-  uint32_t o = (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xb1, 0xf, 0xf, true);
-  v = v > o ? v : o;
-  o = (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4e, 0xf, 0xf, true);
-  return v > o ? v : o;
-}
 
 // Four waves per SIMD (at most 128 VGPRs), as allreduceRmsNormPullKernel.
 template <int DT, int UPL, int NV, int FMT>

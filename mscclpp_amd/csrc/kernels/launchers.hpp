@@ -70,6 +70,13 @@ int allReduceRmsNormMxPullCheck(const mscclppAmdRankView* views, int nviews, int
                                 void* const* resOut, const void* const* gamma, void* const* scale, size_t rows,
                                 size_t cols, int dtype, int format, int& nblocks, int& nthreads, int* upl,
                                 ArNormPullGeom* g);
+int launchAllReduceRmsNormQuant(const mscclppAmdRankView* views, int nviews, int nranks, const void* const* residual,
+                                void* const* resOut, const void* const* gamma, void* const* scale, size_t rows,
+                                size_t cols, int dtype, int format, float eps, int nblocks, int nthreads,
+                                uint64_t budget, hipStream_t s);
+int allReduceRmsNormQuantCheck(const mscclppAmdRankView* views, int nviews, int nranks, const void* const* residual,
+                               void* const* resOut, const void* const* gamma, void* const* scale, size_t rows,
+                               size_t cols, int dtype, int format, int nblocks, int& nthreads, int* upl);
 int launchSendRecv(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdSendRecvOp* ops, int nops,
                    int nblocks, int nthreads, uint64_t budget, hipStream_t s);
 int sendrecvDefaultBlocks(uint64_t bytes);
