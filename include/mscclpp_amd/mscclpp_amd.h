@@ -450,6 +450,33 @@ int mscclppAmdAllReduceRmsNormQuantCheck(const mscclppAmdRankView* views, int nv
                                          const void* const* residual, void* const* resOut, const void* const* gamma,
                                          void* const* scale, size_t rows, size_t cols, int dtype, int format,
                                          int nblocks, int nthreads);
+/* AllReduce (sum) of fp16 / bf16 buffers carried between the GPUs in an OCP microscaling format, one e8m0 scale
+ * byte per block of 32 consecutive elements (kernels/allreduce_quant.hip): a two-shot push through
+ * the bulk scratch, LOSSY.  With Q / D the block quantisation and its inverse,
+ *   out = (DT) D(Q(c_0 + c_1 + ... + c_{n-1})), c_r = D(Q(x_r)) for every rank, the own one included,
+ * the sum in fp32 in rank order.  MSCCLPP_AMD_WIRE_MXINT8: E = e32(amax), code = clamp(RNE(v * 2^(133 - E)), +-127),
+ * dq = code * 2^(E - 133); MSCCLPP_AMD_WIRE_MXFP4: the MXFP4 rule of mscclppAmdAllReduceRmsNormMxPullLaunch.  Per
+ * block |out - sum_r x_r| <= sum_r k amax_r + k amax_s + the n - 1 fp32 roundings + one rounding to DT, k = 2^-6
+ * (mxint8) or 1/2 (mxfp4).  out is a function of the inputs alone: the same bits on every rank, at every grid and
+ * scratch size.  A block that holds a NaN, an infinity or an amax below 2^-126 is unspecified; the others are not
+ * affected and nothing hangs.  Views: input, output, scratch / peerScratch[q] (the BULK scratch, shared with the
+ * fullmesh, RS+AG and pipelined kernels, so calls may alternate), scratchBytes, tokens, peerTokens, expected, err;
+ * no peerInput / peerOutput: nothing of the user's is read or written by a peer.  A scratch below
+ * mscclppAmdAllReduceQuantScratchRequired is worked through in several passes.  out == x is carried.  count: in
+ * elements.  nblocks <= 0: 64 KiB of a rank's slice per workgroup, 1 .. 64, a function of (nranks, count); every
+ * rank must launch the same nblocks.  nthreads <= 0: 512.
+ * 4 (nothing is launched, no device is touched): a dtype other than F16 / BF16, a count of 0 or no multiple of
+ * 32, nranks outside 2..8, an unknown format, null fields, a pointer that is not 16-byte aligned, an output that
+ * overlaps an input or another output otherwise than out == x, a bad launch shape; 5: views whose scratch cannot
+ * hold one step, a workgroup's range beyond 2 GiB (more workgroups carry it), a grid that cannot be resident. */
+#define MSCCLPP_AMD_WIRE_MXINT8 0
+#define MSCCLPP_AMD_WIRE_MXFP4 1
+int mscclppAmdAllReduceQuantLaunch(const mscclppAmdRankView* views, int nviews, int nranks, size_t count, int dtype,
+                                   int format, int nblocks, int nthreads, uint64_t budgetTicks, void* stream);
+/* Scratch bytes per rank of ONE pass over the whole buffer, enough at every grid: regions A and B of nranks images
+ * each, an image being P * 32 (mxint8) or P * 16 (mxfp4) code bytes and P scale bytes padded to 16, P = a slice's
+ * blocks plus the grid's rounding.  0: the call is not carried. */
+size_t mscclppAmdAllReduceQuantScratchRequired(int nranks, size_t count, int dtype, int format);
 /* Send / Recv by a zero-copy pull (kernels/sendrecv.hip): one launch runs a table of point-to-point
  * operations, in table order.  An operation moves `bytes` from `send` on rank `src` to `recv` on
  * rank `dst`: the receiver reads `send` -- the address at which the view of rank `dst` has the
@@ -560,6 +587,16 @@ int mscclppAmdCommAllReduceRmsNormMxPull(ncclComm_t comm, const void* x, void* q
 int mscclppAmdCommAllReduceRmsNormQuant(ncclComm_t comm, const void* x, void* q, void* scale, const void* residual,
                                         void* resOut, const void* gamma, size_t rows, size_t cols, int ncclDtype,
                                         int format, float eps, void* stream);
+/* mscclppAmdAllReduceQuantLaunch on this communicator's bulk scratch: send / recv hold count elements of
+ * ncclFloat16 / ncclBfloat16, recv == send is carried.  Nothing is registered, no algorithm is selected and no
+ * host traffic runs, so it works on any tensor and under stream capture; every rank must make the same call.
+ * Refusals as for the launch entry point; also ncclInvalidArgument on a one-rank communicator.
+ * ncclAllReduce takes this path for fp16 / bf16 ncclSum calls of count % 32 == 0, 16-byte aligned pointers and at
+ * least MSCCLPP_AMD_ALLREDUCE_QUANT_MIN_BYTES when MSCCLPP_AMD_ALLREDUCE_QUANT=mxint8|mxfp4 is set (both read
+ * once); mscclppAmdCommQuantCount counts the calls of either kind that launched it. */
+int mscclppAmdCommAllReduceQuant(ncclComm_t comm, const void* sendbuff, void* recvbuff, size_t count, int ncclDtype,
+                                 int format, void* stream);
+int mscclppAmdCommQuantCount(ncclComm_t comm, uint64_t* count);
 /* Reduce-type code (MSCCLPP_AMD_*) for an ncclDataType_t and accumulation type (-1 = AUTO), or -1. */
 int mscclppAmdReduceType(int ncclDtype, int accumNcclDtype);
 int mscclppAmdCommBarrier(ncclComm_t comm);

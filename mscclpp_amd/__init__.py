@@ -208,6 +208,9 @@ def lib():
                                                  i32, i32, i32],
         "mscclppAmdCommAllReduceRmsNormQuant": [vp, vp, vp, vp, vp, vp, vp, sz, sz, i32, i32, ctypes.c_float, vp],
         "mscclppAmdCommAllToAllLLCount": [vp, ctypes.POINTER(ctypes.c_uint64)],
+        "mscclppAmdAllReduceQuantLaunch": [ctypes.POINTER(RankView), i32, i32, sz, i32, i32, i32, i32, u64, vp],
+        "mscclppAmdCommAllReduceQuant": [vp, vp, vp, sz, i32, i32, vp],
+        "mscclppAmdCommQuantCount": [vp, ctypes.POINTER(ctypes.c_uint64)],
         "mscclppAmdReduceLaunch": [ctypes.POINTER(RankView), i32, i32, sz, i32, i32, i32, i32, i32, u64, vp],
         "ncclReduce": [vp, vp, sz, i32, i32, i32, vp, vp],
         "mscclppAmdPullReduceLaunch": [ctypes.POINTER(RankView), i32, i32, i32, sz, i32, i32, i32, i32, i32, u64, vp],
@@ -273,6 +276,8 @@ def lib():
     L.mscclppAmdAllToAllLLScratchRequired.restype = sz
     L.mscclppAmdAllReduceRmsNormScratchRequired.argtypes = [i32, sz, sz, i32]
     L.mscclppAmdAllReduceRmsNormScratchRequired.restype = sz
+    L.mscclppAmdAllReduceQuantScratchRequired.argtypes = [i32, sz, i32, i32]
+    L.mscclppAmdAllReduceQuantScratchRequired.restype = sz
     for name in ("mscclppAmdExecutionPlanName", "mscclppAmdExecutionPlanCollective"):
         getattr(L, name).argtypes = [vp]
         getattr(L, name).restype = ctypes.c_char_p
@@ -566,6 +571,14 @@ def all_reduce_rms_norm_scratch_required(nranks, rows, cols, dtype_code):
     return lib().mscclppAmdAllReduceRmsNormScratchRequired(nranks, rows, cols, dtype_code)
 
 
+WIRE_FORMATS = {"mxint8": 0, "mxfp4": 1}  # MSCCLPP_AMD_WIRE_MXINT8, MSCCLPP_AMD_WIRE_MXFP4
+
+
+def all_reduce_quant_scratch_required(nranks, count, dtype_code, fmt):
+    """Bulk-scratch bytes per rank of one pass of all_reduce_quant over `count` elements, enough at every grid."""
+    return lib().mscclppAmdAllReduceQuantScratchRequired(nranks, count, dtype_code, WIRE_FORMATS.get(fmt, -1))
+
+
 class InProcessRanks:
     """n ranks of one AllReduce inside this process on one GPU (parity tests).
 
@@ -852,6 +865,19 @@ class InProcessRanks:
                                                            nthreads, budget_ticks, stream_ptr(stream))
         check(code, "in-process all_reduce_rms_norm_quant")
 
+    def all_reduce_quant(self, inputs, outputs, fmt, nblocks=0, nthreads=0, budget_ticks=500_000_000, stream=None):
+        """Sum of the ranks' fp16 / bf16 buffers carried in a block-scaled wire format through the bulk scratch
+        (mscclppAmdAllReduceQuantLaunch): fmt "mxint8" or "mxfp4", one e8m0 scale per 32 elements.  Lossy:
+        out = D(Q(sum_r D(Q(x_r)))) with the sum in fp32 in rank order, the same bits on every rank at every
+        grid and scratch size.  numel % 32 == 0; outputs[r] may be inputs[r]."""
+        if self.bulk is None:
+            raise MscclppError(5, "all_reduce_quant: these ranks hold no bulk scratch")
+        code = lib().mscclppAmdAllReduceQuantLaunch(self.views(inputs, outputs, bulk=True), self.n, self.n,
+                                                    inputs[0].numel(), DTYPE_CODES.get(inputs[0].dtype, -1),
+                                                    WIRE_FORMATS.get(fmt, -1), nblocks, nthreads, budget_ticks,
+                                                    stream_ptr(stream))
+        check(code, "in-process all_reduce_quant")
+
     def send_recv(self, ops, nblocks=0, nthreads=0, budget_ticks=500_000_000, stream=None):
         """ncclSend / ncclRecv (a whole group) for in-process ranks, one launch.  ops: (src, dst, send,
         recv) in table order -- `send` on rank src (a tensor, read in place by rank dst) lands in
@@ -944,6 +970,24 @@ class Communicator:
                                                  nblocks, nthreads, stream_ptr(stream))
         check(code, "ncclAllReduce")
         return recv
+
+    def all_reduce_quant(self, send, recv=None, fmt="mxint8", stream=None):
+        """AllReduce (sum) of an fp16 / bf16 tensor whose payload crosses the links as MXINT8 or MXFP4 blocks
+        (mscclppAmdCommAllReduceQuant; InProcessRanks.all_reduce_quant has the definition).  Lossy.  Nothing is
+        registered, so any tensor and stream capture work; numel % 32 == 0, 16-byte aligned; in place by default."""
+        recv = send if recv is None else recv
+        check(lib().mscclppAmdCommAllReduceQuant(self.comm, ctypes.c_void_p(send.data_ptr()),
+                                                 ctypes.c_void_p(recv.data_ptr()), send.numel(),
+                                                 NCCL_DTYPES.get(send.dtype, -1), WIRE_FORMATS.get(fmt, -1),
+                                                 stream_ptr(stream)), "mscclppAmdCommAllReduceQuant")
+        return recv
+
+    def quant_count(self):
+        """Calls of this communicator that launched the quantised-wire AllReduce: all_reduce_quant, and
+        ncclAllReduce under MSCCLPP_AMD_ALLREDUCE_QUANT (mscclppAmdCommQuantCount)."""
+        c = ctypes.c_uint64()
+        check(lib().mscclppAmdCommQuantCount(self.comm, ctypes.byref(c)), "mscclppAmdCommQuantCount")
+        return int(c.value)
 
     def all_reduce_rms_norm(self, x, gamma, y=None, residual=None, res_out=None, eps=1e-6, stream=None):
         """Fused AllReduce (sum over the ranks, fp32, rank order) + residual add + RMSNorm of a [rows][cols]

@@ -489,6 +489,12 @@ ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, n
            "fp8 e4m3/e5m2 x sum, min, max, avg)");
       return (int)ncclInvalidArgument;
     }
+    // The opt-in to the quantised wire: a function of the call and the environment, so every rank
+    // decides alike.  Everything else takes the selector as before.
+    if (const int fmt = envAllReduceQuant();
+        fmt >= 0 && op == ncclSum && (dt == MSCCLPP_AMD_F16 || dt == MSCCLPP_AMD_BF16) && count % 32 == 0 &&
+        ((uintptr_t)sendbuff | (uintptr_t)recvbuff) % 16 == 0 && bytes >= envAllReduceQuantMinBytes(comm->nranks))
+      return comm->allReduceQuant(sendbuff, recvbuff, count, dt, fmt, (hipStream_t)stream);
     return selectAndExecute(comm, "allreduce", sendbuff, recvbuff, bytes, bytes, bytes, datatype, op, stream);
   });
 }

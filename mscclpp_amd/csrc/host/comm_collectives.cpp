@@ -118,6 +118,23 @@ int ncclComm::allReduceLaunch(const void* in, void* out, size_t bytes, int dtype
   return ncclInvalidArgument;
 }
 
+int ncclComm::allReduceQuant(const void* in, void* out, size_t count, int dtype, int format, hipStream_t stream) {
+  std::lock_guard<std::mutex> lk(mu);
+  mappings.beginLaunch();
+  mscclppAmdRankView v = baseView(in, out);
+  // one pass where the scratch held from init allows it; larger buffers take several, never a re-allocation
+  size_t need = allReduceQuantScratchRequired(nranks, count, dtype, format);
+  if (need > bulkBytes) need = bulkBytes;
+  ensure(bulkScratch, bulkBytes, peerBulk, need, stream);
+  v.scratch = bulkScratch;
+  v.scratchBytes = bulkBytes;
+  for (int r = 0; r < nranks; ++r) v.peerScratch[r] = peerBulk[r];
+  const int rc = launchAllReduceQuant(&v, 1, nranks, count, dtype, format, 0, 0, spinBudgetTicks(), stream);
+  mappings.recordUses(stream, device);
+  if (rc == 0) ++quantCount;
+  return rc;
+}
+
 int ncclComm::bulkCollective(int mode, const void* in, void* out, size_t blockBytes, int dtype, int op, int algo,
                              int nblocks, int nthreads, hipStream_t stream) {
   std::lock_guard<std::mutex> lk(mu);

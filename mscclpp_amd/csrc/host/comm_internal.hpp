@@ -171,6 +171,29 @@ inline int envAlgo() {  // MSCCLPP_AMD_ALGO, read once
   return algo;
 }
 
+// MSCCLPP_AMD_ALLREDUCE_QUANT=mxint8|mxfp4, read once: the wire format ncclAllReduce's opt-in takes (DESIGN.md
+// §17n), or -1 (unset, or any other value: nothing changes).
+inline int envAllReduceQuant() {
+  static const int fmt = [] {
+    const char* e = std::getenv("MSCCLPP_AMD_ALLREDUCE_QUANT");
+    const std::string s(e ? e : "");
+    return s == "mxint8" ? (int)MSCCLPP_AMD_WIRE_MXINT8 : s == "mxfp4" ? (int)MSCCLPP_AMD_WIRE_MXFP4 : -1;
+  }();
+  return fmt;
+}
+
+// MSCCLPP_AMD_ALLREDUCE_QUANT_MIN_BYTES, read once: the smallest message the opt-in takes.  Unset: the default
+// of the rank count, which is "never" at every count until the sweep of §17n has been run on hardware -- no
+// crossover has been measured, so none is claimed.
+inline size_t envAllReduceQuantMinBytes(int nranks) {
+  static const long long env = [] {
+    const char* e = std::getenv("MSCCLPP_AMD_ALLREDUCE_QUANT_MIN_BYTES");
+    return e && *e ? (long long)std::strtoull(e, nullptr, 10) : -1ll;
+  }();
+  (void)nranks;
+  return env >= 0 ? (size_t)env : ~(size_t)0;
+}
+
 }  // namespace host
 }  // namespace mscclpp_amd
 
@@ -372,6 +395,7 @@ struct ncclComm {
   static constexpr int kP2pTag = 3;  // outside the 4k+0..2 tag spaces of core.cpp (memTag, connTag, semTag)
   uint64_t pullLLCount = 0;  // collective calls that took pullReduce's LL path
   uint64_t a2aLLCount = 0;   // ncclAllToAll / ncclAllToAllv calls that took allToAll's LL path
+  uint64_t quantCount = 0;   // calls that launched the quantised-wire AllReduce (allReduceQuant)
   // PreMulSum handles: a handle's value is ncclNumOps + its slot; a destroyed slot is taken again by
   // the next create.  With a vendor communicator the handles are the vendor library's and this
   // table stays empty.
@@ -454,6 +478,9 @@ struct ncclComm {
                 hipStream_t stream);
   int allReduceLaunch(const void* in, void* out, size_t bytes, int dtype, int op, int algo, int nblocks, int nthreads,
                       hipStream_t stream);
+  // The quantised-wire AllReduce (kernels/allreduce_quant.hip) on the bulk scratch and the peers'
+  // bulk mappings: nothing is registered.  count in elements, dtype F16 / BF16, format MSCCLPP_AMD_WIRE_*.
+  int allReduceQuant(const void* in, void* out, size_t count, int dtype, int format, hipStream_t stream);
   // ReduceScatter (mode 1) / AllGather (mode 2) through the bulk all-pairs kernel; `bytes` is the
   // per-rank block (recvcount / sendcount bytes).
   int bulkCollective(int mode, const void* in, void* out, size_t blockBytes, int dtype, int op, int algo, int nblocks,

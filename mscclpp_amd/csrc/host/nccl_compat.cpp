@@ -1045,6 +1045,49 @@ int mscclppAmdCommAllReduceRmsNormQuant(ncclComm_t comm, const void* x, void* q,
   });
 }
 
+// The quantised-wire AllReduce (kernels/allreduce_quant.hip): the views' plumbing is checked here,
+// the buffers, the count, the type and the format by launchAllReduceQuant, all before a device is touched; a refusal
+// launches nothing.
+int mscclppAmdAllReduceQuantLaunch(const mscclppAmdRankView* views, int nviews, int nranks, size_t count, int dtype,
+                                   int format, int nblocks, int nthreads, uint64_t budgetTicks, void* stream) {
+  return guarded([&] {
+    ViewNeeds needs;
+    needs.all = kViewInput | kViewOutput | kViewScratch | kViewHandshake | kViewPeerScratch;
+    if (!viewsValid(views, nviews, nranks, needs)) return (int)ncclInvalidArgument;
+    unsigned seen = 0;
+    for (int i = 0; i < nviews; ++i) {  // no rank twice
+      if ((seen >> views[i].rank) & 1u) return (int)ncclInvalidArgument;
+      seen |= 1u << views[i].rank;
+    }
+    return mscclpp_amd::launchAllReduceQuant(views, nviews, nranks, count, dtype, format, nblocks, nthreads,
+                                             budgetTicks ? budgetTicks : spinBudgetTicks(), (hipStream_t)stream);
+  });
+}
+
+size_t mscclppAmdAllReduceQuantScratchRequired(int nranks, size_t count, int dtype, int format) {
+  return mscclpp_amd::allReduceQuantScratchRequired(nranks, count, dtype, format);
+}
+
+int mscclppAmdCommAllReduceQuant(ncclComm_t comm, const void* sendbuff, void* recvbuff, size_t count, int ncclDtype,
+                                 int format, void* stream) {
+  return guarded([&] {
+    if (!comm || comm->nranks < 2) return (int)ncclInvalidArgument;
+    const int dt = ncclDtype == (int)ncclFloat16 ? MSCCLPP_AMD_F16 : ncclDtype == (int)ncclBfloat16 ? MSCCLPP_AMD_BF16 : -1;
+    // (what launchAllReduceQuant refuses on one view, ahead of the communicator's bookkeeping)
+    if (dt < 0 || !sendbuff || !recvbuff || count == 0 || count % 32 || ((uintptr_t)sendbuff | (uintptr_t)recvbuff) % 16 ||
+        (format != MSCCLPP_AMD_WIRE_MXINT8 && format != MSCCLPP_AMD_WIRE_MXFP4))
+      return (int)ncclInvalidArgument;
+    return comm->allReduceQuant(sendbuff, recvbuff, count, dt, format, (hipStream_t)stream);
+  });
+}
+
+int mscclppAmdCommQuantCount(ncclComm_t comm, uint64_t* count) {
+  if (!comm || !count) return ncclInvalidArgument;
+  std::lock_guard<std::mutex> lk(comm->mu);
+  *count = comm->quantCount;
+  return ncclSuccess;
+}
+
 int mscclppAmdCommAllToAllLLCount(ncclComm_t comm, uint64_t* count) {
   if (!comm || !count) return ncclInvalidArgument;
   std::lock_guard<std::mutex> lk(comm->mu);

@@ -77,6 +77,10 @@ int launchAllReduceRmsNormQuant(const mscclppAmdRankView* views, int nviews, int
 int allReduceRmsNormQuantCheck(const mscclppAmdRankView* views, int nviews, int nranks, const void* const* residual,
                                void* const* resOut, const void* const* gamma, void* const* scale, size_t rows,
                                size_t cols, int dtype, int format, int nblocks, int& nthreads, int* upl);
+int launchAllReduceQuant(const mscclppAmdRankView* views, int nviews, int nranks, size_t count, int dtype, int format,
+                         int nblocks, int nthreads, uint64_t budget, hipStream_t s);
+size_t allReduceQuantScratchRequired(int nranks, size_t count, int dtype, int format);
+int allReduceQuantDefaultBlocks(int nranks, uint64_t count);
 int launchSendRecv(const mscclppAmdRankView* views, int nviews, int nranks, const mscclppAmdSendRecvOp* ops, int nops,
                    int nblocks, int nthreads, uint64_t budget, hipStream_t s);
 int sendrecvDefaultBlocks(uint64_t bytes);
